@@ -1,12 +1,17 @@
 #!/usr/bin/env python
 """bench.py - NAR training sessions/sec on MI355X (BASELINE.json metric), G1-shape synthetic workload.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one optimizer step of the NAR hot path (negative sampling -> features -> CAR -> UGRNN -> scorer ->
 sampled-softmax loss -> backward -> L2 + TF-Adam -> recent-clicks state update) on one batch of 256 sessions PER
 GPU (weak scaling) whose tensors are already resident in HBM.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the line.
+--full adds everything else the line used to carry: host submission cost, the hipGraph replay arm, the per-GEMM roofline with
+its live PMC traffic, the G1-like-lengths leg, the native fp32 MFMA arm, the N > 1 exchange report, the through-the-boundary
+legs, the bf16 / Adressa / stress arms, the CPU baseline and the HitRate / MRR parity check (each still subject to its --no-* flag).
 """
 import argparse
 import json
@@ -167,7 +172,7 @@ def child_arm(args, extra):
     """This script as a child process for another configuration; returns its headline, its G1-like-lengths leg and its roofline entry."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(max(10, min(args.steps, 20))), "--warmup", str(args.warmup),
-           "--seed", str(args.seed), "--no-cpu-baseline", "--no-boundary-leg", "--no-native-arm", "--no-arms", "--graph", "off"] + extra
+           "--seed", str(args.seed), "--full", "--no-cpu-baseline", "--no-boundary-leg", "--no-native-arm", "--no-arms", "--graph", "off"] + extra
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         lines = [x for x in r.stdout.strip().splitlines() if x.startswith("{")]
@@ -328,7 +333,7 @@ def pmc_traffic_live(symbol, seed):
     if not os.path.exists(exe):
         return None, "rocprofv3 not found"
     d = tempfile.mkdtemp(prefix="cham_pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "2", "--warmup", "1", "--seed", str(seed), "--no-cpu-baseline",
+    child = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "2", "--warmup", "1", "--seed", str(seed), "--full", "--no-cpu-baseline",
              "--no-ragged-leg", "--no-boundary-leg", "--no-arms", "--no-native-arm", "--no-pmc", "--graph", "off"]
     vals = {}
     try:
@@ -476,6 +481,41 @@ def dp_exchange_report(dp, one_step, first_step, backend, n=5):
                     "the early bucket [Wf1 .. Ws4] flies under the backward and only its wait is inside"}
 
 
+DUMP_ARRAYS = dict(loss=(np.float64, 16), logits=(np.float32, 1_500_000), probs=(np.float32, 1_500_000), neg_items=(np.float64, 500_000),
+                   params=(np.float32, 8_900_000), grads=(np.float32, 1_000_000), recent_pop_norm=(np.float64, 750_000),
+                   recent_clicks_buffer=(np.float64, 250_000))      # name -> (dtype, element limit); at the limits 63.6e6 bytes, under the cap
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_sample(a, limit, seed):
+    """a as is when it has at most `limit` elements, else a fixed sample of `limit` of its flattened elements (seeded: the same
+    positions for the same size in every run)."""
+    if a.size <= limit:
+        return a
+    return np.ascontiguousarray(a).reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, limit, replace=False))]
+
+
+def dump_outputs(d, model, rt, state, loss):
+    """--dump-outputs DIR: what the timed path handed its caller in its LAST timed step, as DIR/<name>.npy (float32 / float64) - the
+    loss [total, xe, reg], the logits and softmax probabilities [B, T, 1 + N] and negative item ids [B, T, N] of this rank's rows, the
+    weights after the Adam update and a sample of the gradients they were updated with, and the recent-clicks state after the update.
+    Inputs are seeded, so two builds run with the same arguments compare output for output.  -> {name: shape}"""
+    os.makedirs(d, exist_ok=True)
+    o = model.outputs_numpy()
+    arrays = {"loss": loss, "logits": o['logits'], "probs": o['probs'], "neg_items": o['neg_items'], "params": rt.flat.cpu().numpy(),
+              "grads": rt.grads.cpu().numpy(), "recent_pop_norm": state.get_articles_recent_pop_norm(),
+              "recent_clicks_buffer": state.get_recent_clicks_buffer()}
+    shapes, total = {}, 0
+    for i, (name, a) in enumerate(arrays.items()):
+        dtype, limit = DUMP_ARRAYS[name]
+        a = dump_sample(np.asarray(a).astype(dtype, copy=False), limit, seed=1000 + i)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes exceed the %d-byte cap" % (total, DUMP_MAX_BYTES)
+        np.save(os.path.join(d, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -509,8 +549,17 @@ def main():
     ap.add_argument("--graph", default="arm", choices=["arm", "on", "off"],
                     help="the step replayed from ONE captured hipGraph (nar_model.GraphedTrainStep; bit-identical to the eager step).  arm (default): "
                          "the timed steps are eager - measured faster on ROCm 7.2: the graph's nodes overlap less than the hand-scheduled lanes, "
-                         "profiles/r06_notes.md section 3 - and the replay is timed as an extra leg (hip_graph_arm); on: the timed steps ARE replays")
+                         "profiles/r06_notes.md section 3 - and the replay is timed as an extra leg (hip_graph_arm, --full); on: the timed steps ARE replays")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg and check (host submission cost, hipGraph arm, roofline + PMC traffic, G1-like-lengths "
+                         "leg, native fp32 MFMA arm, N > 1 exchange report, through-the-boundary legs, bf16 / Adressa / stress arms, CPU baseline, "
+                         "HitRate / MRR parity); off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, logits, probabilities, negatives, updated weights, a gradient sample, "
+                         "recent-clicks state) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line, the JSON record: until it is printed, file descriptor 1 points at stderr, so that nothing a library
     # writes at C level (librccl prints a version banner through stdio when a communicator is created) can end up next to it
@@ -633,190 +682,190 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     loss = dp.global_loss().cpu().numpy()
+    dumped = dump_outputs(args.dump_outputs, model, rt, state, loss) if args.dump_outputs and rank == 0 else None
 
-    # ---- host-side cost of submitting a step (Python + ctypes + HIP launches, no synchronisation): what bounds the step once the GPU
-    # is faster than the host (bf16 / short ragged batches)
-    torch.cuda.synchronize()
-    t_h = time.perf_counter()
-    for i in range(3):
-        one_step(args.warmup + args.steps + 100 + i)
-    host_enqueue_ms = (time.perf_counter() - t_h) / 3 * 1e3
-    torch.cuda.synchronize()
-    host_enqueue_eager_ms = host_enqueue_ms
-    if args.graph == "arm" and world == 1 and args.state == "device":
-        graph["arm"] = hip_graph_arm(model, state, dev_batches, one_step, args.warmup + args.steps + 3, Bg, gstep)
-    if gstep[0] is not None:         # the legs below (per-launch HIP events, arms) drive the EAGER step; its host cost beside the replay's
-        graph["graph_replays_timed"] = gstep[0].replays
-        gstep[0] = None
+    # ---- everything below the headline: --full only
+    if args.full:
+        # ---- host-side cost of submitting a step (Python + ctypes + HIP launches, no synchronisation): what bounds the step once the GPU
+        # is faster than the host (bf16 / short ragged batches)
+        torch.cuda.synchronize()
         t_h = time.perf_counter()
         for i in range(3):
-            one_step(args.warmup + args.steps + 103 + i)
-        host_enqueue_eager_ms = (time.perf_counter() - t_h) / 3 * 1e3
+            one_step(args.warmup + args.steps + 100 + i)
+        host_enqueue_ms = (time.perf_counter() - t_h) / 3 * 1e3
         torch.cuda.synchronize()
+        host_enqueue_eager_ms = host_enqueue_ms
+        if args.graph == "arm" and world == 1 and args.state == "device":
+            graph["arm"] = hip_graph_arm(model, state, dev_batches, one_step, args.warmup + args.steps + 3, Bg, gstep)
+        if gstep[0] is not None:         # the legs below (per-launch HIP events, arms) drive the EAGER step; its host cost beside the replay's
+            graph["graph_replays_timed"] = gstep[0].replays
+            gstep[0] = None
+            t_h = time.perf_counter()
+            for i in range(3):
+                one_step(args.warmup + args.steps + 103 + i)
+            host_enqueue_eager_ms = (time.perf_counter() - t_h) / 3 * 1e3
+            torch.cuda.synchronize()
 
-    # ---- roofline leg: HIP-event timing of every GEMM launch over a few extra steps -------------------------
-    rt.profile = []
-    nprof = 3
-    for i in range(nprof):
-        one_step(args.warmup + args.steps + i)
-    torch.cuda.synchronize()
-    prof, rt.profile = rt.profile, None
-    # Per kernel SYMBOL (rebuilt from the library's record of each launch: tile instance + epilogue variant), aggregated over all of
-    # its launches exactly like `rocprofv3 --stats` aggregates, so avg_launch_ms is comparable with the committed kernel_stats.  The
-    # roofline object describes the symbol with the LARGEST total time; the top three are listed beside it.
-    by_sym = {}
-    for r in prof:
-        if r['tile'] < 0:
-            continue
-        e = by_sym.setdefault(gemm_symbol(r), dict(n=0, ms=0.0, flop=0.0, bytes=0.0, r=r, shapes={}))
-        if r['M'] * r['N'] * r['K'] > e['r']['M'] * e['r']['N'] * e['r']['K']:
-            e['r'] = r
-        t_ms = r['ev'][0].elapsed_time(r['ev'][1])
-        e['n'] += 1
-        e['ms'] += t_ms
-        e['flop'] += 2.0 * r['M'] * r['N'] * r['K']
-        sh = e['shapes'].setdefault((r['M'], r['N'], r['K']), [0, 0.0])
-        sh[0] += 1; sh[1] += t_ms
-        # operands + output, each touched once: A + B + bias + C (+ the saved activation a dgrad epilogue reads); fp32 storage, or
-        # bf16 operands / saved activations and a bf16 or fp32 output for the bf16-resident kernels
-        if r.get('dmf') and r.get('bf16'):      # the bf16 twin: every matrix one bf16 array
-            e['bytes'] += 2.0 * r['M'] * r['K'] + 2.0 * r['K'] * r['N'] + 2.0 * r['M'] * r['N'] + 2.0 * r['M'] * r['N']
-        elif r.get('dmf'):      # dS1 in, Z2c in, the planes out (6 B per element as three bf16 planes, 4 B as two fp16 planes), pred / dpred / b2 partials per position
-            e['bytes'] += 4.0 * r['M'] * r['K'] + 6.0 * r['K'] * r['N'] + 4.0 * r['M'] * r['N'] + (4.0 if r.get('h2out') else 6.0) * r['M'] * r['N']
-        elif r.get('h2'):       # operands as two fp16 planes (4 B per element), fp32 output, the dgrad reads the activation's h plane
-            e['bytes'] += 4.0 * (r['M'] * r['K'] + r['K'] * r['N']) + 4.0 * r['M'] * r['N'] + (2.0 * r['M'] * r['N'] if r['dref'] else 0) + \
-                (4.0 * r['N'] if r['bias'] else 0)
-        elif r.get('p3'):       # operands as three bf16 planes (6 B per element), fp32 output, the dgrad reads the activation's h plane
-            e['bytes'] += 6.0 * (r['M'] * r['K'] + r['K'] * r['N']) + 4.0 * r['M'] * r['N'] + (2.0 * r['M'] * r['N'] if r['dref'] else 0) + \
-                (4.0 * r['N'] if r['bias'] else 0)
-        elif r.get('b16') or r.get('b1'):
-            e['bytes'] += 2.0 * (r['M'] * r['K'] + r['K'] * r['N'] + (r['M'] * r['N'] if r['dref'] else 0)) + \
-                (4.0 if (r['out_f32'] or r['epi'] == 6) else 2.0) * r['M'] * r['N'] + (4.0 * r['N'] if r['bias'] else 0)
-        else:
-            e['bytes'] += 4.0 * (r['M'] * r['K'] + r['K'] * r['N'] + r['M'] * r['N'] * (2 if r['dref'] else 1) + (r['N'] if r['bias'] else 0))
-    ranked = sorted(by_sym.items(), key=lambda kv: -kv[1]['ms'])
-    ms_all = sum(e['ms'] for e in by_sym.values())
-    fl_all = sum(e['flop'] for e in by_sym.values())
+        # ---- roofline leg: HIP-event timing of every GEMM launch over a few extra steps -------------------------
+        rt.profile = []
+        nprof = 3
+        for i in range(nprof):
+            one_step(args.warmup + args.steps + i)
+        torch.cuda.synchronize()
+        prof, rt.profile = rt.profile, None
+        # Per kernel SYMBOL (rebuilt from the library's record of each launch: tile instance + epilogue variant), aggregated over all of
+        # its launches exactly like `rocprofv3 --stats` aggregates, so avg_launch_ms is comparable with the committed kernel_stats.  The
+        # roofline object describes the symbol with the LARGEST total time; the top three are listed beside it.
+        by_sym = {}
+        for r in prof:
+            if r['tile'] < 0:
+                continue
+            e = by_sym.setdefault(gemm_symbol(r), dict(n=0, ms=0.0, flop=0.0, bytes=0.0, r=r, shapes={}))
+            if r['M'] * r['N'] * r['K'] > e['r']['M'] * e['r']['N'] * e['r']['K']:
+                e['r'] = r
+            t_ms = r['ev'][0].elapsed_time(r['ev'][1])
+            e['n'] += 1
+            e['ms'] += t_ms
+            e['flop'] += 2.0 * r['M'] * r['N'] * r['K']
+            sh = e['shapes'].setdefault((r['M'], r['N'], r['K']), [0, 0.0])
+            sh[0] += 1; sh[1] += t_ms
+            # operands + output, each touched once: A + B + bias + C (+ the saved activation a dgrad epilogue reads); fp32 storage, or
+            # bf16 operands / saved activations and a bf16 or fp32 output for the bf16-resident kernels
+            if r.get('dmf') and r.get('bf16'):      # the bf16 twin: every matrix one bf16 array
+                e['bytes'] += 2.0 * r['M'] * r['K'] + 2.0 * r['K'] * r['N'] + 2.0 * r['M'] * r['N'] + 2.0 * r['M'] * r['N']
+            elif r.get('dmf'):      # dS1 in, Z2c in, the planes out (6 B per element as three bf16 planes, 4 B as two fp16 planes), pred / dpred / b2 partials per position
+                e['bytes'] += 4.0 * r['M'] * r['K'] + 6.0 * r['K'] * r['N'] + 4.0 * r['M'] * r['N'] + (4.0 if r.get('h2out') else 6.0) * r['M'] * r['N']
+            elif r.get('h2'):       # operands as two fp16 planes (4 B per element), fp32 output, the dgrad reads the activation's h plane
+                e['bytes'] += 4.0 * (r['M'] * r['K'] + r['K'] * r['N']) + 4.0 * r['M'] * r['N'] + (2.0 * r['M'] * r['N'] if r['dref'] else 0) + \
+                    (4.0 * r['N'] if r['bias'] else 0)
+            elif r.get('p3'):       # operands as three bf16 planes (6 B per element), fp32 output, the dgrad reads the activation's h plane
+                e['bytes'] += 6.0 * (r['M'] * r['K'] + r['K'] * r['N']) + 4.0 * r['M'] * r['N'] + (2.0 * r['M'] * r['N'] if r['dref'] else 0) + \
+                    (4.0 * r['N'] if r['bias'] else 0)
+            elif r.get('b16') or r.get('b1'):
+                e['bytes'] += 2.0 * (r['M'] * r['K'] + r['K'] * r['N'] + (r['M'] * r['N'] if r['dref'] else 0)) + \
+                    (4.0 if (r['out_f32'] or r['epi'] == 6) else 2.0) * r['M'] * r['N'] + (4.0 * r['N'] if r['bias'] else 0)
+            else:
+                e['bytes'] += 4.0 * (r['M'] * r['K'] + r['K'] * r['N'] + r['M'] * r['N'] * (2 if r['dref'] else 1) + (r['N'] if r['bias'] else 0))
+        ranked = sorted(by_sym.items(), key=lambda kv: -kv[1]['ms'])
+        ms_all = sum(e['ms'] for e in by_sym.values())
+        fl_all = sum(e['flop'] for e in by_sym.values())
 
-    def describe(sym, e):
-        r = e['r']
-        mode = "NN" if not r['transA'] and not r['transB'] else ("TN (wgrad)" if r['transA'] else
-                                                                 ("NT (dgrad)" if r['dref'] or not r['bias'] else "NT (forward, transposed weight shadow)"))
-        return "%s = %s MFMA GEMM, %s, %s%s; M,N,K of its largest launch %d,%d,%d" % (
-            sym, ("bf16-resident, LDS-DMA staging" if r.get('b1') else "bf16-resident" if r.get('b16') else "bf16 (fp32 storage, rounded while staged)") if r['bf16'] else
-            ("fp32-grade (operands resident in HBM as two fp16 planes x a power-of-two scale written by their producers, three fp16 MFMA "
-             "products per fp32 product, fp32 accumulate, LDS-DMA staging)" if r.get('h2') else
-             "fp32-grade (operands resident in HBM as three bf16 planes written by their producers, six bf16 MFMA products per fp32 product, "
-             "fp32 accumulate, LDS-DMA staging)" if r.get('p3') else
-             "fp32-grade (two fp16 planes x a power-of-two scale per operand, split while staged, three fp16 MFMA products per fp32 product, "
-             "fp32 accumulate)" if r.get('x2h') else
-             "fp32 (three bf16 planes per operand, six bf16 MFMA products per fp32 product, fp32 accumulate)" if r.get('x3') else "fp32"), mode, EPI_NAMES.get(r['epi'], "?"), ", row-scale prologue" if r['rowscale'] else "",
-            r['M'], r['N'], r['K'])
+        def describe(sym, e):
+            r = e['r']
+            mode = "NN" if not r['transA'] and not r['transB'] else ("TN (wgrad)" if r['transA'] else
+                                                                     ("NT (dgrad)" if r['dref'] or not r['bias'] else "NT (forward, transposed weight shadow)"))
+            return "%s = %s MFMA GEMM, %s, %s%s; M,N,K of its largest launch %d,%d,%d" % (
+                sym, ("bf16-resident, LDS-DMA staging" if r.get('b1') else "bf16-resident" if r.get('b16') else "bf16 (fp32 storage, rounded while staged)") if r['bf16'] else
+                ("fp32-grade (operands resident in HBM as two fp16 planes x a power-of-two scale written by their producers, three fp16 MFMA "
+                 "products per fp32 product, fp32 accumulate, LDS-DMA staging)" if r.get('h2') else
+                 "fp32-grade (operands resident in HBM as three bf16 planes written by their producers, six bf16 MFMA products per fp32 product, "
+                 "fp32 accumulate, LDS-DMA staging)" if r.get('p3') else
+                 "fp32-grade (two fp16 planes x a power-of-two scale per operand, split while staged, three fp16 MFMA products per fp32 product, "
+                 "fp32 accumulate)" if r.get('x2h') else
+                 "fp32 (three bf16 planes per operand, six bf16 MFMA products per fp32 product, fp32 accumulate)" if r.get('x3') else "fp32"), mode, EPI_NAMES.get(r['epi'], "?"), ", row-scale prologue" if r['rowscale'] else "",
+                r['M'], r['N'], r['K'])
 
-    def gemm_entry(sym, e):
-        tf_s = e['flop'] / (e['ms'] * 1e-3) / 1e12
-        gbs = e['bytes'] / (e['ms'] * 1e-3) / 1e9
-        peak = BF16_MATRIX_PEAK_TFLOPS if e['r']['bf16'] else (H2_MATRIX_PEAK_TFLOPS if (e['r'].get('h2') or e['r'].get('x2h') or e['r'].get('f16p')) else
-                                                               X3_MATRIX_PEAK_TFLOPS if (e['r'].get('x3') or e['r'].get('p3') or e['r'].get('dmf')) else FP32_MATRIX_PEAK_TFLOPS)
-        return {"kernel": describe(sym, e), "launches_per_step": round(e['n'] / nprof, 2), "avg_launch_ms": round(e['ms'] / e['n'], 4),
-                "ms_per_step": round(e['ms'] / nprof, 3), "tflops": round(tf_s, 2), "frac_of_mfma_peak": round(tf_s / peak, 4),
-                "mfma_peak_tflops": round(peak, 1), "algorithmic_GBps": round(gbs, 1), "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBPS, 4),
-                # one symbol can serve launches of very different shapes (e.g. the CAR dgrad and a K = 64 scorer dgrad): per shape
-                "by_shape": [{"M": m, "N": n_, "K": k, "launches_per_step": round(c / nprof, 2), "avg_launch_ms": round(t / c, 4),
-                              "tflops": round(2.0 * m * n_ * k / (t / c * 1e-3) / 1e12, 2),
-                              "frac_of_mfma_peak": round(2.0 * m * n_ * k / (t / c * 1e-3) / 1e12 / peak, 4)}
-                             for (m, n_, k), (c, t) in sorted(e['shapes'].items(), key=lambda kv: -kv[1][1])[:3]]}
-    DOM_SYMBOL, dom = ranked[0] if ranked else ("", dict(n=1, ms=1.0, flop=0.0, bytes=0.0, r=None))
-    n_nn, ms_nn, fl_nn = dom['n'], dom['ms'], dom['flop']
-    dom_h2 = bool(dom['r'] and dom['r'].get('h2'))
-    dom_x3 = bool(dom['r'] and (dom['r'].get('x3') or dom['r'].get('p3')))
-    dom_peak = H2_MATRIX_PEAK_TFLOPS if dom_h2 else (X3_MATRIX_PEAK_TFLOPS if dom_x3 else FP32_MATRIX_PEAK_TFLOPS)
-    achieved = fl_nn / (ms_nn * 1e-3) / 1e12 if ms_nn > 0 else 0.0
-    # roofline.traffic: measured in THIS run by two rocprofv3 counter passes over a short child run (pmc_traffic_live) on the default line;
-    # otherwise (child arms, --no-pmc, no rocprofv3) the newest committed profiles/*_pmc_traffic.json, LABELLED as such - and a symbol that
-    # is missing from it is reported in `traffic_error`, never silently null
-    traffic, traffic_src, traffic_err = None, None, None
-    headline = args.config == "g1" and world == 1 and args.scaling == "weak" and args.dtype == "f32"
-    if rank == 0 and headline and not args.no_pmc and not args.no_arms:
-        traffic, traffic_src = pmc_traffic_live(DOM_SYMBOL, args.seed)
-        if traffic is None:
-            traffic_err, traffic_src = traffic_src, None
-    if traffic is None and headline:
-        for fn in sorted(os.listdir(os.path.join(ROOT, "profiles")), reverse=True) if os.path.isdir(os.path.join(ROOT, "profiles")) else []:
-            if fn.endswith("_pmc_traffic.json"):
-                pmc = json.load(open(os.path.join(ROOT, "profiles", fn)))
-                rec = pmc.get(DOM_SYMBOL)
-                if rec:
-                    traffic = rec["traffic_bytes_per_launch"]
-                    traffic_src = "committed profile, NOT measured in this run: profiles/%s (%s)" % (fn, pmc.get("_generated_by", "scripts/pmc_traffic.py"))
-                else:
-                    traffic_err = ((traffic_err + "; ") if traffic_err else "") + "kernel symbol %r is not in profiles/%s" % (DOM_SYMBOL, fn)
-                    print("bench.py: roofline.traffic unavailable - %s" % traffic_err, file=sys.stderr)
-                break
+        def gemm_entry(sym, e):
+            tf_s = e['flop'] / (e['ms'] * 1e-3) / 1e12
+            gbs = e['bytes'] / (e['ms'] * 1e-3) / 1e9
+            peak = BF16_MATRIX_PEAK_TFLOPS if e['r']['bf16'] else (H2_MATRIX_PEAK_TFLOPS if (e['r'].get('h2') or e['r'].get('x2h') or e['r'].get('f16p')) else
+                                                                   X3_MATRIX_PEAK_TFLOPS if (e['r'].get('x3') or e['r'].get('p3') or e['r'].get('dmf')) else FP32_MATRIX_PEAK_TFLOPS)
+            return {"kernel": describe(sym, e), "launches_per_step": round(e['n'] / nprof, 2), "avg_launch_ms": round(e['ms'] / e['n'], 4),
+                    "ms_per_step": round(e['ms'] / nprof, 3), "tflops": round(tf_s, 2), "frac_of_mfma_peak": round(tf_s / peak, 4),
+                    "mfma_peak_tflops": round(peak, 1), "algorithmic_GBps": round(gbs, 1), "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBPS, 4),
+                    # one symbol can serve launches of very different shapes (e.g. the CAR dgrad and a K = 64 scorer dgrad): per shape
+                    "by_shape": [{"M": m, "N": n_, "K": k, "launches_per_step": round(c / nprof, 2), "avg_launch_ms": round(t / c, 4),
+                                  "tflops": round(2.0 * m * n_ * k / (t / c * 1e-3) / 1e12, 2),
+                                  "frac_of_mfma_peak": round(2.0 * m * n_ * k / (t / c * 1e-3) / 1e12 / peak, 4)}
+                                 for (m, n_, k), (c, t) in sorted(e['shapes'].items(), key=lambda kv: -kv[1][1])[:3]]}
+        DOM_SYMBOL, dom = ranked[0] if ranked else ("", dict(n=1, ms=1.0, flop=0.0, bytes=0.0, r=None))
+        n_nn, ms_nn, fl_nn = dom['n'], dom['ms'], dom['flop']
+        dom_h2 = bool(dom['r'] and dom['r'].get('h2'))
+        dom_x3 = bool(dom['r'] and (dom['r'].get('x3') or dom['r'].get('p3')))
+        dom_peak = H2_MATRIX_PEAK_TFLOPS if dom_h2 else (X3_MATRIX_PEAK_TFLOPS if dom_x3 else FP32_MATRIX_PEAK_TFLOPS)
+        achieved = fl_nn / (ms_nn * 1e-3) / 1e12 if ms_nn > 0 else 0.0
+        # roofline.traffic: measured in THIS run by two rocprofv3 counter passes over a short child run (pmc_traffic_live) on the default line;
+        # otherwise (child arms, --no-pmc, no rocprofv3) the newest committed profiles/*_pmc_traffic.json, LABELLED as such - and a symbol that
+        # is missing from it is reported in `traffic_error`, never silently null
+        traffic, traffic_src, traffic_err = None, None, None
+        headline = args.config == "g1" and world == 1 and args.scaling == "weak" and args.dtype == "f32"
+        if rank == 0 and headline and not args.no_pmc and not args.no_arms:
+            traffic, traffic_src = pmc_traffic_live(DOM_SYMBOL, args.seed)
+            if traffic is None:
+                traffic_err, traffic_src = traffic_src, None
+        if traffic is None and headline:
+            for fn in sorted(os.listdir(os.path.join(ROOT, "profiles")), reverse=True) if os.path.isdir(os.path.join(ROOT, "profiles")) else []:
+                if fn.endswith("_pmc_traffic.json"):
+                    pmc = json.load(open(os.path.join(ROOT, "profiles", fn)))
+                    rec = pmc.get(DOM_SYMBOL)
+                    if rec:
+                        traffic = rec["traffic_bytes_per_launch"]
+                        traffic_src = "committed profile, NOT measured in this run: profiles/%s (%s)" % (fn, pmc.get("_generated_by", "scripts/pmc_traffic.py"))
+                    else:
+                        traffic_err = ((traffic_err + "; ") if traffic_err else "") + "kernel symbol %r is not in profiles/%s" % (DOM_SYMBOL, fn)
+                        print("bench.py: roofline.traffic unavailable - %s" % traffic_err, file=sys.stderr)
+                    break
 
-    # ---- secondary leg: the same step on G1-LIKE session lengths (2 + min(Geometric(0.45), seq_len - 2), mean
-    # ~4 clicks, zero-padded to the batch maximum).  The headline above is the "all sessions full length" stress/roofline
-    # variant (no padded positions: the most work a session can carry); with ragged sessions the step runs its row-wise
-    # stages on the valid positions only (nar_model.upload_batch), so sessions/s rises with the padding fraction.
-    ragged = None
-    if args.length_dist == "full" and args.state == "device" and not args.no_ragged_leg:
-        rb = synthetic.make_batches(n_distinct, Bg, cfg['seq_len'], cfg['n_items'], params['session_features_config'],
-                                    seed=args.seed + 1, length_dist="g1", sessions_per_hour=Bg * 2)
-        rdev = [dp.upload(f, l) for f, l in rb]
+        # ---- secondary leg: the same step on G1-LIKE session lengths (2 + min(Geometric(0.45), seq_len - 2), mean
+        # ~4 clicks, zero-padded to the batch maximum).  The headline above is the "all sessions full length" stress/roofline
+        # variant (no padded positions: the most work a session can carry); with ragged sessions the step runs its row-wise
+        # stages on the valid positions only (nar_model.upload_batch), so sessions/s rises with the padding fraction.
+        ragged = None
+        if args.length_dist == "full" and args.state == "device" and not args.no_ragged_leg:
+            rb = synthetic.make_batches(n_distinct, Bg, cfg['seq_len'], cfg['n_items'], params['session_features_config'],
+                                        seed=args.seed + 1, length_dist="g1", sessions_per_hour=Bg * 2)
+            rdev = [dp.upload(f, l) for f, l in rb]
 
-        def ragged_step(i):
-            k = i % n_distinct
-            model.feed_state(state, state)
-            model.train_step(rdev[k])
-            state.update_from_device_batch(rdev[k]['aci'], rdev[k]['g_event_ts'])
-            model.presample(rdev[(k + 1) % n_distinct])
-        for i in range(max(n_distinct, args.warmup)):        # every distinct padded length T allocates its StepPlan once
-            ragged_step(i)
-        barrier()
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            ragged_step(args.warmup + i)
-        barrier()
-        rdt = time.perf_counter() - t0
-        if world > 1:
-            tt = torch.tensor([rdt], dtype=torch.float64, device="cuda")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            rdt = float(tt.item())
-        ragged = {"session_lengths": "g1: 2 + min(Geometric(0.45), seq_len - 2), zero-padded to the batch maximum",
-                  "value": round(Bg * args.steps / rdt, 2), "unit": "sessions/s", "ms_per_step": round(rdt / args.steps * 1e3, 3),
-                  "mean_clicks_per_session": round(float(np.mean([np.asarray(f['session_size']).mean() for f, _ in rb])), 2),
-                  "valid_positions_of_padded": round(float(sum(d['P'] for d in rdev)) / float(sum(d['B'] * d['T'] for d in rdev)), 4),
-                  "padded_T": [int(d['T']) for d in rdev]}
+            def ragged_step(i):
+                k = i % n_distinct
+                model.feed_state(state, state)
+                model.train_step(rdev[k])
+                state.update_from_device_batch(rdev[k]['aci'], rdev[k]['g_event_ts'])
+                model.presample(rdev[(k + 1) % n_distinct])
+            for i in range(max(n_distinct, args.warmup)):        # every distinct padded length T allocates its StepPlan once
+                ragged_step(i)
+            barrier()
+            t0 = time.perf_counter()
+            for i in range(args.steps):
+                ragged_step(args.warmup + i)
+            barrier()
+            rdt = time.perf_counter() - t0
+            if world > 1:
+                tt = torch.tensor([rdt], dtype=torch.float64, device="cuda")
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                rdt = float(tt.item())
+            ragged = {"session_lengths": "g1: 2 + min(Geometric(0.45), seq_len - 2), zero-padded to the batch maximum",
+                      "value": round(Bg * args.steps / rdt, 2), "unit": "sessions/s", "ms_per_step": round(rdt / args.steps * 1e3, 3),
+                      "mean_clicks_per_session": round(float(np.mean([np.asarray(f['session_size']).mean() for f, _ in rb])), 2),
+                      "valid_positions_of_padded": round(float(sum(d['P'] for d in rdev)) / float(sum(d['B'] * d['T'] for d in rdev)), 4),
+                      "padded_T": [int(d['T']) for d in rdev]}
 
-    # ---- comparison leg (default fp32 arithmetic only): the SAME runtime, weights and batches with the plane-product GEMMs switched off,
-    # i.e. every GEMM on v_mfma_f32_32x32x2_f32 - so the line carries both arms measured in one run
-    native_arm = None
-    if args.dtype == "f32" and getattr(rt, 'x3', False) and not args.no_native_arm:
-        had_p3, rt.x3, rt.p3 = rt.p3, False, False       # p3 off as well: the plane-resident CAR GEMMs are plane products too
-        n_arm = max(5, min(args.steps, 10))
-        for i in range(3):
-            one_step(args.warmup + args.steps + 200 + i)
-        barrier()
-        t0 = time.perf_counter()
-        for i in range(n_arm):
-            one_step(args.warmup + args.steps + 203 + i)
-        barrier()
-        adt = time.perf_counter() - t0
-        rt.x3, rt.p3 = True, had_p3
-        if world > 1:
-            tt = torch.tensor([adt], dtype=torch.float64, device="cuda")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            adt = float(tt.item())
-        native_arm = {"gemm": "every GEMM on v_mfma_f32_32x32x2_f32 (--dtype f32_native), same runtime / weights / batches", "steps": n_arm,
-                      "value": round(Bg * n_arm / adt, 2), "unit": "sessions/s", "ms_per_step": round(adt / n_arm * 1e3, 3)}
+        # ---- comparison leg (default fp32 arithmetic only): the SAME runtime, weights and batches with the plane-product GEMMs switched off,
+        # i.e. every GEMM on v_mfma_f32_32x32x2_f32 - so the line carries both arms measured in one run
+        native_arm = None
+        if args.dtype == "f32" and getattr(rt, 'x3', False) and not args.no_native_arm:
+            had_p3, rt.x3, rt.p3 = rt.p3, False, False       # p3 off as well: the plane-resident CAR GEMMs are plane products too
+            n_arm = max(5, min(args.steps, 10))
+            for i in range(3):
+                one_step(args.warmup + args.steps + 200 + i)
+            barrier()
+            t0 = time.perf_counter()
+            for i in range(n_arm):
+                one_step(args.warmup + args.steps + 203 + i)
+            barrier()
+            adt = time.perf_counter() - t0
+            rt.x3, rt.p3 = True, had_p3
+            if world > 1:
+                tt = torch.tensor([adt], dtype=torch.float64, device="cuda")
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                adt = float(tt.item())
+            native_arm = {"gemm": "every GEMM on v_mfma_f32_32x32x2_f32 (--dtype f32_native), same runtime / weights / batches", "steps": n_arm,
+                          "value": round(Bg * n_arm / adt, 2), "unit": "sessions/s", "ms_per_step": round(adt / n_arm * 1e3, 3)}
 
-    # ---- N > 1: what the exchange is and what it cost (every rank takes part: collectives - never under `if rank == 0`)
-    dp_info = dp_exchange_report(dp, one_step, args.warmup + args.steps + 200, backend) if world > 1 else None
+        # ---- N > 1: what the exchange is and what it cost (every rank takes part: collectives - never under `if rank == 0`)
+        dp_info = dp_exchange_report(dp, one_step, args.warmup + args.steps + 200, backend) if world > 1 else None
 
     if rank == 0:
-        L = rt.layout
-        T = cfg['seq_len'] - 1
-        dense_fwd = dense_step_flops(Bl, T, cfg['neg'], L.F, cfg['C'], cfg['H'], cfg.get('rnn_num_layers', 1))
         ms_step = dt / args.steps * 1e3
         out = {
             "metric": "NAR training sessions/sec", "value": round(Bg * args.steps / dt, 2), "unit": "sessions/s",
@@ -843,26 +892,32 @@ def main():
                                         "(csrc/gemm_x3.hip); N <= 64 on v_mfma_f32_32x32x2_f32"),
                                 "f32_native": "every GEMM on v_mfma_f32_32x32x2_f32",
                                 "bf16": "bf16-resident candidate-row matrices, fp32 accumulate"}[args.dtype],
-                       "host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
-                       "host_enqueue_ms_per_step_eager": round(host_enqueue_eager_ms, 3),
+                       **({"host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
+                           "host_enqueue_ms_per_step_eager": round(host_enqueue_eager_ms, 3)} if args.full else {}),
                        "hip_graph": graph,
                        "rnn_coop_spin_timeouts": int(rt.rnn_coop_timed_out()),       # bounded spins of the cooperative recurrent kernels (ragged leg): must be 0
                        "final_loss": [round(float(x), 5) for x in loss]},
-            "roofline": {"bound": "mfma", "kernel": describe(DOM_SYMBOL, dom) + " - the GEMM symbol with the largest total time in the step",
-                         "achieved": round(achieved, 2), "peak": round(dom_peak, 1), "unit": "TFLOP/s",
-                         "peak_note": ("fp16 dense MFMA peak 2500 TFLOP/s / 3 plane products per fp32 product; algorithmic fp32 FLOPs in `achieved` "
-                                       "(the native fp32 MFMA peak is %.1f)" % FP32_MATRIX_PEAK_TFLOPS) if dom_h2 else
-                                      ("bf16 dense MFMA peak 2500 TFLOP/s / 6 plane products per fp32 product; algorithmic fp32 FLOPs in `achieved` "
-                                       "(the native fp32 MFMA peak is %.1f)" % FP32_MATRIX_PEAK_TFLOPS) if dom_x3 else "fp32 dense MFMA peak",
-                         "frac": round(achieved / dom_peak, 4), "traffic": traffic, "traffic_source": traffic_src, "traffic_error": traffic_err,
-                         "launches_per_step": round(n_nn / nprof, 2), "avg_launch_ms": round(ms_nn / max(1, n_nn), 4),
-                         "algorithmic_gflop_per_launch": round(fl_nn / max(1, n_nn) / 1e9, 3),
-                         "algorithmic_bytes_per_launch": round(dom['bytes'] / max(1, n_nn)),
-                         "top_gemms": [gemm_entry(sym, e) for sym, e in ranked[:3]],
-                         "all_gemm_ms_per_step": round(ms_all / nprof, 3),
-                         "all_gemm_tflops": round(fl_all / (ms_all * 1e-3) / 1e12, 2) if ms_all > 0 else 0.0,
-                         "step_reference_dense_tflops": round(3 * dense_fwd / (ms_step * 1e-3) / 1e12, 2)},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if rank == 0 and args.full:
+        L = rt.layout
+        T = cfg['seq_len'] - 1
+        dense_fwd = dense_step_flops(Bl, T, cfg['neg'], L.F, cfg['C'], cfg['H'], cfg.get('rnn_num_layers', 1))
+        out["roofline"] = {"bound": "mfma", "kernel": describe(DOM_SYMBOL, dom) + " - the GEMM symbol with the largest total time in the step",
+                           "achieved": round(achieved, 2), "peak": round(dom_peak, 1), "unit": "TFLOP/s",
+                           "peak_note": ("fp16 dense MFMA peak 2500 TFLOP/s / 3 plane products per fp32 product; algorithmic fp32 FLOPs in `achieved` "
+                                         "(the native fp32 MFMA peak is %.1f)" % FP32_MATRIX_PEAK_TFLOPS) if dom_h2 else
+                                        ("bf16 dense MFMA peak 2500 TFLOP/s / 6 plane products per fp32 product; algorithmic fp32 FLOPs in `achieved` "
+                                         "(the native fp32 MFMA peak is %.1f)" % FP32_MATRIX_PEAK_TFLOPS) if dom_x3 else "fp32 dense MFMA peak",
+                           "frac": round(achieved / dom_peak, 4), "traffic": traffic, "traffic_source": traffic_src, "traffic_error": traffic_err,
+                           "launches_per_step": round(n_nn / nprof, 2), "avg_launch_ms": round(ms_nn / max(1, n_nn), 4),
+                           "algorithmic_gflop_per_launch": round(fl_nn / max(1, n_nn) / 1e9, 3),
+                           "algorithmic_bytes_per_launch": round(dom['bytes'] / max(1, n_nn)),
+                           "top_gemms": [gemm_entry(sym, e) for sym, e in ranked[:3]],
+                           "all_gemm_ms_per_step": round(ms_all / nprof, 3),
+                           "all_gemm_tflops": round(fl_all / (ms_all * 1e-3) / 1e12, 2) if ms_all > 0 else 0.0,
+                           "step_reference_dense_tflops": round(3 * dense_fwd / (ms_step * 1e-3) / 1e12, 2)}
         if args.dtype == "bf16":     # bf16 MFMA is 16x the fp32 rate: name whichever roof binds the dominant launch at its shape
             t_mfma, t_hbm = fl_nn / (BF16_MATRIX_PEAK_TFLOPS * 1e12), dom['bytes'] / (HBM_PEAK_GBPS * 1e9)
             if t_hbm > t_mfma:

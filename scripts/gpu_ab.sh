@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; T=${TAG:-r05ab}; O=$R/gpurun_out/$T; mkdir -p $O; 
 BARGS=${BARGS:-"--steps 20 --warmup 5 --no-cpu-baseline --no-boundary-leg --no-arms --no-native-arm --no-pmc"}
 for rep in $(seq 1 ${REPS:-2}); do
   for arm in $AB; do
-    ( env $(echo $arm | tr '+' ' ') timeout 300 python bench.py $BARGS 2>$O/$arm.err | grep '^{' | tail -1 ) >> $O/$arm.jsonl
+    ( env $(echo $arm | tr '+' ' ') timeout 300 python bench.py --full $BARGS 2>$O/$arm.err | grep '^{' | tail -1 ) >> $O/$arm.jsonl
   done
 done
 python - <<PY

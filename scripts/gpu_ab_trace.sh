@@ -6,12 +6,12 @@ BARGS=${BARGS:-"--steps 20 --warmup 5 --no-cpu-baseline --no-boundary-leg --no-a
 for rep in $(seq 1 ${REPS:-2}); do
   for arm in $AB; do
     cd $R
-    ( env $(echo $arm | tr '+' ' ') timeout 300 python bench.py $BARGS 2>$O/$arm.err | grep '^{' | tail -1 ) >> $O/$arm.jsonl
+    ( env $(echo $arm | tr '+' ' ') timeout 300 python bench.py --full $BARGS 2>$O/$arm.err | grep '^{' | tail -1 ) >> $O/$arm.jsonl
   done
 done
 for arm in $AB; do
   cd /tmp
-  ( env $(echo $arm | tr '+' ' ') timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$arm -o p -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-boundary-leg --no-arms --no-native-arm --no-pmc --no-ragged-leg 2>&1 | grep '^{' | tail -1 ) > $O/profiled_$arm.json
+  ( env $(echo $arm | tr '+' ' ') timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$arm -o p -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-boundary-leg --no-arms --no-native-arm --no-pmc --no-ragged-leg 2>&1 | grep '^{' | tail -1 ) > $O/profiled_$arm.json
   f=$(find $O/prof_$arm -name '*kernel_stats.csv' | head -1)
   cp $f "$O/${arm}_kernel_stats.csv" 2>/dev/null
   rm -rf $O/prof_$arm

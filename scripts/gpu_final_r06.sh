@@ -6,16 +6,16 @@
 # Everything lands in gpurun_out/$T/; scripts/collect_profiles_r06.sh copies what is judged to profiles/r06_*.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; T=${TAG:-r06}; O=$R/gpurun_out/$T; mkdir -p $O; cd $R; export TMPDIR=/tmp PYTHONPATH=$R
 ( timeout 200 python -c 'import __graft_entry__ as g; g.smoke()' 2>&1 | tail -3 ) > $O/smoke.log
-PMCARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-ragged-leg --no-boundary-leg --no-arms --no-native-arm --no-pmc --graph off"
+PMCARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-ragged-leg --no-boundary-leg --no-arms --no-native-arm --no-pmc --graph off"
 cd /tmp
 ( timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o fetch -- python $R/bench.py $PMCARGS 2>&1 | tail -2 ) > $O/pmc_fetch.log
 ( timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o write -- python $R/bench.py $PMCARGS 2>&1 | tail -2 ) > $O/pmc_write.log
 cd $R
 PMC_GENERATED_BY=scripts/gpu_final_r06.sh python scripts/pmc_traffic.py $(find $O/pmc_fetch -name '*counter_collection.csv' | head -1) $(find $O/pmc_write -name '*counter_collection.csv' | head -1) > $O/pmc_traffic.json 2>$O/pmc_traffic.err
 rm -rf $O/pmc_fetch $O/pmc_write
-( timeout 1500 python bench.py 2>$O/bench.err | grep '^{' | tail -1 ) > $O/bench.json
+( timeout 1500 python bench.py --full 2>$O/bench.err | grep '^{' | tail -1 ) > $O/bench.json
 cd /tmp
-BARGS="--steps 10 --warmup 3 --no-cpu-baseline --no-ragged-leg --no-boundary-leg --no-arms --no-native-arm --no-pmc --graph off"
+BARGS="--full --steps 10 --warmup 3 --no-cpu-baseline --no-ragged-leg --no-boundary-leg --no-arms --no-native-arm --no-pmc --graph off"
 ( timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o $T -- python $R/bench.py $BARGS 2>&1 | grep '^{' | tail -1 ) > $O/bench_profiled.json
 cp $(find $O/prof -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv 2>/dev/null
 python $R/scripts/timeline.py $(find $O/prof -name '*kernel_trace.csv' | head -1) k_sel_count_valid full > $O/kernel_trace_step.txt 2>&1

@@ -7,7 +7,7 @@ D=${DTYPE:-f32}
 mkdir -p $O
 export TMPDIR=/tmp PYTHONPATH=$R
 cd /tmp
-( timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -o $T -- python $R/bench.py --dtype $D --steps 10 --warmup 3 --no-cpu-baseline --no-ragged-leg --no-boundary-leg ${BENCH_ARGS:-} 2>&1 | grep '^{' | tail -1 ) > $O/bench_profiled_$T.log
+( timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -o $T -- python $R/bench.py --full --dtype $D --steps 10 --warmup 3 --no-cpu-baseline --no-ragged-leg --no-boundary-leg ${BENCH_ARGS:-} 2>&1 | grep '^{' | tail -1 ) > $O/bench_profiled_$T.log
 cd $R
 f=$(find $O/prof_$T -name '*kernel_stats.csv' | head -1)
 cp $f $O/prof_${T}_kernel_stats.csv 2>/dev/null

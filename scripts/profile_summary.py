@@ -17,7 +17,7 @@ def main():
     r = b["roofline"]
     out = ["# %s - summary of the committed measurement artifacts (1 x MI355X)\n" % tag]
     out.append("| | |\n|---|---|")
-    out.append("| command | `python bench.py --gpus 1 --steps %d --warmup %d` (`%s_bench.json`) |" % (b["steps"], b["warmup"], tag))
+    out.append("| command | `python bench.py --gpus 1 --steps %d --warmup %d --full` (`%s_bench.json`) |" % (b["steps"], b["warmup"], tag))
     out.append("| %s | **%.0f %s**, %.3f ms/step, dtype %s, %s |" % (b["metric"], b["value"], b["unit"], b["ms_per_step"], b["dtype"], b["config"]["workload"]))
     g = b.get("g1_like_session_lengths")
     if g:
@@ -38,7 +38,7 @@ def main():
         if os.path.exists(fn):
             x = json.load(open(fn))
             out.append("| %s | %.0f sessions/s, %.3f ms/step (`%s`) |" % (label, x["value"], x["ms_per_step"], os.path.basename(fn)))
-    out.append("\n## rocprofv3 --kernel-trace --stats of `bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-ragged-leg` (`%s_kernel_stats.csv`)\n" % tag)
+    out.append("\n## rocprofv3 --kernel-trace --stats of `bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-ragged-leg` (`%s_kernel_stats.csv`)\n" % tag)
     rows = list(csv.DictReader(open(os.path.join(P, tag + "_kernel_stats.csv"))))
     # optimizer steps in the profiled run = launches of the Adam kernel (warm-up + timed + host-enqueue + roofline-leg steps)
     steps = float(next((int(x["Calls"]) for x in rows if x["Name"].startswith("k_adam_tf")), 16))

@@ -72,3 +72,17 @@ def test_no_collective_under_a_rank0_branch_of_bench():
             walk(n, under_rank0)
     walk(tree, False)
     assert not bad, bad
+
+
+def test_dump_outputs_stay_under_the_cap():
+    """--dump-outputs: every array at its element limit still fits the 64 MB cap; a sampled array takes the same positions in every run
+    (two builds compare output for output)."""
+    import bench
+    assert sum(np.dtype(t).itemsize * n for t, n in bench.DUMP_ARRAYS.values()) <= bench.DUMP_MAX_BYTES
+    assert all(np.dtype(t) in (np.float32, np.float64) for t, _ in bench.DUMP_ARRAYS.values())
+    n = bench.DUMP_ARRAYS["grads"][1]
+    a = np.arange(3 * n, dtype=np.float32)
+    s1, s2 = bench.dump_sample(a, n, 7), bench.dump_sample(a.copy(), n, 7)
+    assert s1.shape == (n,) and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    small = np.ones((4, 5), np.float32)
+    assert bench.dump_sample(small, 20, 7) is small

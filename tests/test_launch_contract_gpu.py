@@ -23,7 +23,7 @@ def _launch(n, extra, env_extra):
     env = dict(os.environ, CHAM_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=ROOT, **env_extra)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "2",
-           "--no-cpu-baseline", "--no-boundary-leg", "--no-ragged-leg", "--no-native-arm", "--no-arms", "--no-pmc"] + extra
+           "--full", "--no-cpu-baseline", "--no-boundary-leg", "--no-ragged-leg", "--no-native-arm", "--no-arms", "--no-pmc"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, "rc %d\n%s" % (r.returncode, r.stderr[-3000:])
     lines = [x for x in r.stdout.splitlines() if x.strip()]
