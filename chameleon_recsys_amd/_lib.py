@@ -125,6 +125,10 @@ _SIGNATURES = {
     "cham_loss_accumulate": (c_int, [P, P, c_int, P]),
     "cham_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cham_colsum": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P]),
+    "cham_eval_beyond_accuracy": (c_int, [P, c_int, P, P, c_int, P, c_int, c_int64, P, c_int, c_float, c_float, P, P, P, P]),
+    "cham_eval_coverage_seed": (c_int, [P, c_int, c_int64, P, P, P]),
+    "cham_eval_coverage_workspace_bytes": (c_size_t, [c_int64]),
+    "cham_eval_coverage_count": (c_int, [P, P, c_int64, P, c_size_t, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

@@ -20,6 +20,7 @@ from .. import _roctx
 from .._lib import check, ptr
 from .clicked_items_state import lane_stream
 from .layout import COL_ITEMEMB, ParamLayout
+from .metrics import BEYOND_ACCURACY_PER_CLICK, ItemCoverage
 
 ACT_NONE, ACT_LEAKY, ACT_TANH = 0, 1, 2
 
@@ -968,6 +969,8 @@ class NARModuleModel:
         self.train = self.train_step           # the reference's ``model.train`` op
         self._eval_iter = 0
         self._eval = None
+        self._ba = None                        # enable_beyond_accuracy_metrics: launch scalars; _ba_buffers: maps, counts, per-click values
+        self._ba_buffers = None
         # attributes ItemsStateUpdaterHook fetches / feeds (nar_model.py:1435-1467)
         inp = lambda k: Tensor(k, lambda: np.asarray(self.inputs[k]))
         self.item_clicked = inp('item_clicked')
@@ -1977,12 +1980,62 @@ class NARModuleModel:
 
     def evaluate_step(self, device_batch=None):
         """EVAL-mode ``session.run``: forward with the eval negative-sample counts (nar_trainer_gcom.py:240-242) +
-        rank_items_by_predicted_prob (nar_model.py:777-794)."""
+        rank_items_by_predicted_prob (nar_model.py:777-794) [+ the beyond-accuracy metrics of the ranked lists]."""
         d = device_batch if device_batch is not None else self.upload_batch(self.inputs, self.labels)
         pl = self.forward(d)
         self._rank_items(pl, d)
+        if self._ba is not None:
+            self._beyond_accuracy(d)
         self._eval_iter += 1
         return self.total_loss
+
+    # ------------------------------------------------------------------ beyond-accuracy evaluation metrics (csrc/eval_metrics.hip)
+    def enable_beyond_accuracy_metrics(self, topn, relevance_positive_sample, relevance_negative_samples, recent_clicks_buffer):
+        """From now on every evaluate_step also computes ESI-R, ESI-RR, EILD-R and EILD-RR of its ranked top-n lists and marks the
+        coverage maps (cham_eval_beyond_accuracy).  The maps live on the device until the next call, which re-seeds them: the
+        clicked map from ``recent_clicks_buffer`` - the device state's ring buffer (read in place) or a host array."""
+        if not 2 <= topn <= 64:
+            raise ValueError("the beyond-accuracy metrics need 2 <= eval_metrics_top_n <= 64 (got %d)" % topn)
+        rt, lib, n_items = self.rt, self.rt.lib, self.rt.n_items
+        ba = self._ba_buffers
+        if ba is None:
+            ba = self._ba_buffers = dict(
+                rec=torch.zeros(n_items, dtype=torch.uint8, device=rt.device), clk=torch.zeros(n_items, dtype=torch.uint8, device=rt.device),
+                ws=torch.empty(lib.cham_eval_coverage_workspace_bytes(n_items), dtype=torch.uint8, device=rt.device),
+                counts=torch.zeros(2, dtype=torch.int64, device=rt.device), per_click=None)
+        if isinstance(recent_clicks_buffer, torch.Tensor):
+            buf = recent_clicks_buffer
+        else:
+            buf = torch.from_numpy(np.ascontiguousarray(recent_clicks_buffer, dtype=np.int64).reshape(-1)).to(rt.device)
+        ba['seed'] = buf                          # (kept alive until the seed launch has run)
+        check(lib.cham_eval_coverage_seed(ptr(buf), buf.numel(), n_items, ptr(ba['rec']), ptr(ba['clk']), _stream()),
+              "cham_eval_coverage_seed")
+        self._ba = dict(topn=int(topn), rel_pos=float(relevance_positive_sample), rel_neg=float(relevance_negative_samples))
+
+    def _beyond_accuracy(self, d):
+        """Per-click beyond-accuracy values of the ranked lists of this eval step + the coverage counts, on the current stream."""
+        rt, lib, ba, ev = self.rt, self.rt.lib, self._ba_buffers, self._eval
+        B, T, NC = ev['pred_ids'].shape
+        if ba['per_click'] is None or ba['per_click'].shape[0] != B * T:
+            ba['per_click'] = torch.empty(B * T, 4, dtype=torch.float32, device=rt.device)
+        st = self._dev_state
+        check(lib.cham_eval_beyond_accuracy(ptr(ev['pred_ids']), NC, ptr(d['label_next']), ptr(d['item_clicked']), B * T, ptr(rt.ace),
+                                            rt.ace.shape[1], rt.n_items, ptr(st['pop_norm']), self._ba['topn'], self._ba['rel_pos'],
+                                            self._ba['rel_neg'], ptr(ba['per_click']), ptr(ba['rec']), ptr(ba['clk']), _stream()),
+              "cham_eval_beyond_accuracy")
+        check(lib.cham_eval_coverage_count(ptr(ba['rec']), ptr(ba['clk']), rt.n_items, ptr(ba['ws']), ba['ws'].numel(), ptr(ba['counts']),
+                                           _stream()), "cham_eval_coverage_count")
+        if st.get('device'):
+            self.articles_recent_pop_norm.note_consumed(d['aci'])      # pop_norm is read up to here: the state update waits for this
+        self._ba_shape = (B, T)
+
+    def beyond_accuracy_outputs(self):
+        """(per_click [B, T, 4] float32 = ESI-R, ESI-RR, EILD-R, EILD-RR (0 at padded positions), (recommended, clicked) item counts
+        of the coverage maps) after the last evaluate_step: the two device-to-host reads of the feature per batch."""
+        ba = self._ba_buffers
+        per_click = ba['per_click'].view(*self._ba_shape, 4).cpu().numpy()
+        rec, clk = ba['counts'].cpu().tolist()
+        return per_click, (rec, clk)
 
     def run_step(self):
         """What ``session.run(train_op | eval fetches)`` does for the current value of the input handles."""
@@ -2138,6 +2191,9 @@ class GraphedTrainStep:
         return m.total_loss
 
 
+_DEVICE_FED_METRICS = (ItemCoverage,) + BEYOND_ACCURACY_PER_CLICK     # fed by cham_eval_beyond_accuracy, not update_metrics
+
+
 class ItemsStateUpdaterHook:
     """SessionRunHook around every step (nar_model.py:1369-1700), NAR-path subset:
       * before_run (:1434-1470): feeds ``articles_recent_pop_norm`` / ``pop_recent_items_buffer`` (+ the ACE matrix and
@@ -2148,15 +2204,19 @@ class ItemsStateUpdaterHook:
       * begin / end (:1410-1431, :1669-1695): state snapshot around evaluation, metrics appended to
         ``eval_sessions_metrics_log``;
       * ``eval_metrics_by_session_position`` (HitRate@n per click position, :1718) and ``eval_cold_start`` (steps between an
-        item's first click and its first top-n recommendation, :1480-1494, 1621-1625, 1662-1666; runs in TRAIN and EVAL).
+        item's first click and its first top-n recommendation, :1480-1494, 1621-1625, 1662-1666; runs in TRAIN and EVAL);
+      * ``eval_beyond_accuracy_metrics`` (off by default; the reference always builds them, :1709-1719): NDCG@n on the host, and
+        item coverage, ESI-R / ESI-RR (novelty) and content EILD-R / EILD-RR (diversity, relevance of the negatives =
+        ``eval_negative_sample_relevance``) from cham_eval_beyond_accuracy, which reads the ranked ids, the ACE matrix, the
+        ``articles_recent_pop_norm`` this batch was fed and the coverage maps seeded from the recent-clicks buffer at begin().
     Out of scope: the baseline recommenders (``eval_benchmark_classifiers`` must be empty), the
-    co-occurrence matrix (:1650), novelty / diversity / coverage metrics."""
+    co-occurrence matrix (:1650), the metrics the reference defines but does not instantiate."""
 
     def __init__(self, mode, model, eval_metrics_top_n, clicked_items_state, eval_sessions_metrics_log,
                  sessions_negative_items_log=None, sessions_chameleon_recommendations_log=None,
                  content_article_embeddings_matrix=None, articles_metadata=None, eval_negative_sample_relevance=None,
                  eval_benchmark_classifiers=[], eval_metrics_by_session_position=False, eval_cold_start=False,
-                 eval_metric_ops=None):
+                 eval_metric_ops=None, eval_beyond_accuracy_metrics=False):
         if eval_benchmark_classifiers:
             raise NotImplementedError("baseline recommenders (nar/benchmarks) are out of scope: pass --disable_eval_benchmarks")
         self.eval_cold_start = eval_cold_start
@@ -2170,13 +2230,23 @@ class ItemsStateUpdaterHook:
         self.content_article_embeddings_matrix = content_article_embeddings_matrix
         self.articles_metadata = articles_metadata or {}
         self.eval_metric_ops = eval_metric_ops or {}
+        self.eval_negative_sample_relevance = eval_negative_sample_relevance
+        self.eval_beyond_accuracy_metrics = eval_beyond_accuracy_metrics
 
     def begin(self):
         if self.mode == ModeKeys.EVAL:
-            from .metrics import HitRate, HitRateBySessionPosition, MRR
+            from .metrics import HitRate, HitRateBySessionPosition, MRR, create_beyond_accuracy_metrics
             self.clicked_items_state.save_state_checkpoint()                    # nar_model.py:1415
             self.eval_streaming_metrics_last = {}
             self.streaming_metrics = [HitRate(self.eval_metrics_top_n), MRR(self.eval_metrics_top_n)]       # create_eval_metrics, :1696-1721
+            if self.eval_beyond_accuracy_metrics:
+                st = self.clicked_items_state
+                host_buffer = st.get_recent_clicks_buffer()
+                self.streaming_metrics += create_beyond_accuracy_metrics(self.eval_metrics_top_n, self.eval_negative_sample_relevance,
+                                                                         self.content_article_embeddings_matrix, host_buffer)
+                # the coverage maps are seeded from the same ring buffer: in place when it is in HBM
+                self.model.enable_beyond_accuracy_metrics(self.eval_metrics_top_n, 1.0, self.eval_negative_sample_relevance,
+                                                          st.buf_ids if getattr(st, 'is_device', False) else host_buffer)
             if self.eval_metrics_by_session_position:
                 self.streaming_metrics.append(HitRateBySessionPosition(self.eval_metrics_top_n))
             self.stats_logs = []
@@ -2241,8 +2311,17 @@ class ItemsStateUpdaterHook:
             labels_norm_pop = preds_norm_pop = None
             if self.eval_metrics_by_session_position:                          # nar_model.py:1590-1593
                 labels_norm_pop = self.clicked_items_state.get_articles_recent_pop_norm()[next_item_labels]
+            on_device = [m for m in self.streaming_metrics if isinstance(m, _DEVICE_FED_METRICS)]
             update_metrics(predicted_item_ids, next_item_labels, labels_norm_pop, preds_norm_pop, clicked_items,
-                           self.streaming_metrics, recommender='chameleon')
+                           [m for m in self.streaming_metrics if not isinstance(m, _DEVICE_FED_METRICS)], recommender='chameleon')
+            if on_device:                        # computed by evaluate_step (cham_eval_beyond_accuracy) from this batch's fed state
+                per_click, counts = self.model.beyond_accuracy_outputs()
+                valid = np.asarray(next_item_labels) != 0
+                for m in on_device:
+                    if isinstance(m, ItemCoverage):
+                        m.add_counts(*counts)
+                    else:
+                        m.add_values(per_click[..., BEYOND_ACCURACY_PER_CLICK.index(type(m))][valid])
             self.eval_streaming_metrics_last.update(compute_metrics_results(self.streaming_metrics, recommender='chameleon'))
         if self.eval_cold_start:                                               # nar_model.py:1621-1625, both modes
             self.update_items_cold_start_state(r['user_id'], clicked_items, next_item_labels, r['eval_batch_negative_items'],

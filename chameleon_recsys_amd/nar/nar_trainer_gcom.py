@@ -92,6 +92,9 @@ def define_flags():
            "operand yields NaN where fp32 yields +-inf - behind a tanh layer the native path saturates to a finite +-1 instead - and "
            "operands below 2^-100 lose their lowest plane; tests/test_gemm_p3_gpu.py pins both); f32_native: every GEMM on the native "
            "fp32 MFMA; bf16: bf16-resident candidate-row matrices, fp32 accumulate")
+    a('--eval_beyond_accuracy_metrics', type=_bool, default=False, nargs='?', const=True,
+      help="also report NDCG@n, item coverage, ESI-R / ESI-RR novelty and content EILD-R / EILD-RR diversity (the reference's "
+           "create_eval_metrics list, nar_model.py:1709-1719; computed on the GPU); --eval_negative_sample_relevance weights the -RR pair")
     a('--clicked_items_state', default='host', choices=['host', 'device'], help="keep the recent-clicks state in host numpy (reference "
       "class) or in HBM (bit-identical, no host round trip per step)")
     return ap
@@ -210,7 +213,8 @@ def nar_module_model_fn(features, labels, mode, params):
                                    eval_negative_sample_relevance=params['eval_negative_sample_relevance'],
                                    eval_benchmark_classifiers=[],
                                    eval_metrics_by_session_position=params['eval_metrics_by_session_position'],
-                                   eval_cold_start=params['eval_cold_start'], eval_metric_ops=eval_metrics)]
+                                   eval_cold_start=params['eval_cold_start'], eval_metric_ops=eval_metrics,
+                                   eval_beyond_accuracy_metrics=params.get('eval_beyond_accuracy_metrics', False))]
     if mode == ModeKeys.TRAIN:
         return EstimatorSpec(mode, loss=model.loss_t, train_op=model.train, training_chief_hooks=hooks)
     return EstimatorSpec(mode, loss=model.loss_t, eval_metric_ops=eval_metrics, evaluation_hooks=hooks)
@@ -237,6 +241,7 @@ def build_estimator(model_dir, content_article_embeddings_matrix, articles_metad
         'eval_metrics_by_session_position': FLAGS.eval_metrics_by_session_position,
         'novelty_reg_factor': FLAGS.novelty_reg_factor, 'diversity_reg_factor': FLAGS.diversity_reg_factor,
         'eval_negative_sample_relevance': FLAGS.eval_negative_sample_relevance, 'eval_cold_start': FLAGS.eval_cold_start,
+        'eval_beyond_accuracy_metrics': FLAGS.eval_beyond_accuracy_metrics,
         'session_features_config': session_features_config, 'articles_features_config': articles_features_config,
         'articles_metadata': articles_metadata, 'content_article_embeddings_matrix': content_article_embeddings_matrix})
 

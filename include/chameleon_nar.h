@@ -483,6 +483,24 @@ int cham_loss_finalize_dev(const float* nll, int BT, const void* scalars, const 
 int cham_adam_tf_dev(float* params, const float* grads, float* m, float* v, size_t n, size_t n_reg, float lambda, const void* scalars,
                      float beta1, float beta2, float eps, void* stream);
 
+
+/* --- beyond-accuracy evaluation metrics (reference metrics.py ESI-R :226-266, ESI-RR :269-314, content EILD-R :513-569,
+ * EILD-RR :573-641, ItemCoverage :317-343), csrc/eval_metrics.hip.  pred_ids [BT, NC] ranked candidate ids (cham_rank_items),
+ * labels [BT] (0 = padded position), clicked [BT] item_clicked or NULL, ace [n_items, D] fp32 (row pitch D), pop_norm [n_items]
+ * fp32; n = min(topn, NC) in [2, 64].  per_click [BT, 4] = {ESI-R, ESI-RR, EILD-R, EILD-RR} (0 at padded positions); relevance =
+ * rel_pos where the candidate equals the label, rel_neg otherwise.  Fixed summation order, no atomics: bit-reproducible.
+ * rec_map / clk_map [n_items] bytes (both NULL: no coverage bookkeeping): the top-n ids of valid clicks are marked recommended,
+ * the non-zero labels and clicked items clicked. */
+int cham_eval_beyond_accuracy(const int64_t* pred_ids, int NC, const int64_t* labels, const int64_t* clicked, int BT, const float* ace,
+                              int D, int64_t n_items, const float* pop_norm, int topn, float rel_pos, float rel_neg, float* per_click,
+                              uint8_t* rec_map, uint8_t* clk_map, void* stream);
+/* zeroes both coverage maps, then marks the n_buf ids of the recent-clicks buffer (0 for empty slots included) as clicked */
+int cham_eval_coverage_seed(const int64_t* buffer_ids, int n_buf, int64_t n_items, uint8_t* rec_map, uint8_t* clk_map, void* stream);
+/* counts[2] (device int64) = number of non-zero bytes of {rec_map, clk_map}; maps 16-byte aligned; integer reduction */
+size_t cham_eval_coverage_workspace_bytes(int64_t n_items);
+int cham_eval_coverage_count(const uint8_t* rec_map, const uint8_t* clk_map, int64_t n_items, void* workspace, size_t workspace_bytes,
+                             int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
