@@ -17,78 +17,7 @@ import torch
 from chameleon_recsys_amd.nar import synthetic
 from oracle.nar_oracle import NAROracle
 from tests import helpers as H
-
-
-def _sig(x):
-    return 1.0 / (1.0 + np.exp(-x))
-
-
-def ugrnn_bptt(x, lengths, K, b, R):
-    """tf.contrib.rnn.UGRNNCell (TF 1.12 rnn_cell.py): [g_act, c_act] = [x, h] K + b; c = tanh(c_act); g = sigmoid(g_act + 1);
-    h' = g h + (1 - g) c.  dynamic_rnn: beyond a row's length the output is zero and the state is carried.  loss = sum(out * R).
-    Returns out and d loss / d (x, K, b)."""
-    B, T, I = x.shape
-    H_ = K.shape[1] // 2
-    h = np.zeros((B, H_)); hs, gs, cs, outs = [], [], [], []
-    for t in range(T):
-        z = np.concatenate([x[:, t], h], 1) @ K + b
-        c, g = np.tanh(z[:, H_:]), _sig(z[:, :H_] + 1.0)
-        hn = g * h + (1 - g) * c
-        v = (t < lengths)[:, None]
-        hs.append(h); gs.append(g); cs.append(c)
-        outs.append(np.where(v, hn, 0.0)); h = np.where(v, hn, h)
-    out = np.stack(outs, 1)
-    dx, dK, db, dh = np.zeros_like(x), np.zeros_like(K), np.zeros_like(b), np.zeros((B, H_))
-    for t in range(T - 1, -1, -1):
-        v = (t < lengths)[:, None]
-        dhn = np.where(v, R[:, t] + dh, 0.0)             # output path + state path (both only where the step is valid)
-        carry = np.where(v, 0.0, dh)                      # invalid step: state carried through unchanged
-        g, c, hp = gs[t], cs[t], hs[t]
-        dg, dc = dhn * (hp - c), dhn * (1 - g)
-        dz = np.concatenate([dg * g * (1 - g), dc * (1 - c * c)], 1)
-        xin = np.concatenate([x[:, t], hp], 1)
-        dK += xin.T @ dz; db += dz.sum(0)
-        dxin = dz @ K.T
-        dx[:, t] = dxin[:, :I]
-        dh = carry + dhn * g + dxin[:, I:]
-    return out, dx, dK, db
-
-
-def gru_bptt(x, lengths, Kg, bg, Kc, bc, R):
-    """tf.nn.rnn_cell.GRUCell (TF 1.12): [r, u] = sigmoid([x, h] Kg + bg); c = tanh([x, r h] Kc + bc); h' = u h + (1 - u) c."""
-    B, T, I = x.shape
-    H_ = Kc.shape[1]
-    h = np.zeros((B, H_)); st, outs = [], []
-    for t in range(T):
-        ru = _sig(np.concatenate([x[:, t], h], 1) @ Kg + bg)
-        r, u = ru[:, :H_], ru[:, H_:]
-        c = np.tanh(np.concatenate([x[:, t], r * h], 1) @ Kc + bc)
-        hn = u * h + (1 - u) * c
-        v = (t < lengths)[:, None]
-        st.append((h, r, u, c))
-        outs.append(np.where(v, hn, 0.0)); h = np.where(v, hn, h)
-    out = np.stack(outs, 1)
-    dx = np.zeros_like(x); dKg, dbg, dKc, dbc = np.zeros_like(Kg), np.zeros_like(bg), np.zeros_like(Kc), np.zeros_like(bc)
-    dh = np.zeros((B, H_))
-    for t in range(T - 1, -1, -1):
-        v = (t < lengths)[:, None]
-        hp, r, u, c = st[t]
-        dhn = np.where(v, R[:, t] + dh, 0.0)
-        carry = np.where(v, 0.0, dh)
-        du, dc = dhn * (hp - c), dhn * (1 - u)
-        dzc = dc * (1 - c * c)
-        xc = np.concatenate([x[:, t], r * hp], 1)
-        dKc += xc.T @ dzc; dbc += dzc.sum(0)
-        dxc = dzc @ Kc.T
-        drh = dxc[:, I:]
-        dr = drh * hp
-        dzg = np.concatenate([dr * r * (1 - r), du * u * (1 - u)], 1)
-        xg = np.concatenate([x[:, t], hp], 1)
-        dKg += xg.T @ dzg; dbg += dzg.sum(0)
-        dxg = dzg @ Kg.T
-        dx[:, t] = dxc[:, :I] + dxg[:, :I]
-        dh = carry + dhn * u + drh * r + dxg[:, I:]
-    return out, dx, (dKg, dbg, dKc, dbc)
+from tests.rnn_reference import gru_bptt, ugrnn_bptt
 
 
 def _oracle(cell, layers=1, Hn=24, C=16):
