@@ -868,6 +868,8 @@ extern "C" int cham_rank_items(const float* probs, const int64_t* label_next, co
     if (!probs || !label_next || !neg_ids || !mask || !pred_ids || !pred_probs || !label_rank || BT <= 0 || N <= 0 || N > 8191)
         return -CHAM_ERR_ARG;
     const size_t smem = (size_t)4 * (N + 1) * sizeof(float);
+    // N <= 8191: four waves x (1 + N) probabilities = at most 128 KB of the CU's 160 KB of LDS; beyond 64 KB the limit has to be raised first
+    if (smem > 64 * 1024) CHAM_SET_DYNAMIC_LDS(k_rank_items, 128 * 1024);
     hipLaunchKernelGGL(k_rank_items, dim3((BT + 3) / 4), dim3(256), smem, (hipStream_t)stream, probs, label_next, neg_ids, mask, BT,
                        N, pred_ids, pred_probs, label_rank);
     CHAM_CHECK_LAUNCH();

@@ -421,7 +421,9 @@ int cham_score_softmax_bwd(const float* S3, int K3, const float* w4, const float
 
 /* evaluation: rank_items_by_predicted_prob, nar_model.py:777-794 (tf.nn.top_k over 1+N: descending, lowest index wins
  * ties).  pred_ids/pred_probs [BT, 1+N]; label_rank[bt] = 0-based rank of the positive, -1 for padded clicks - the input of
- * HitRate@n / MRR@n (metrics.py:40-66, 109-134; TF twins nar_model.py:826-835, 859-885) */
+ * HitRate@n / MRR@n (metrics.py:40-66, 109-134; TF twins nar_model.py:826-835, 859-885).  1 <= N <= 8191 (a workgroup keeps the
+ * probabilities of four clicks in LDS: 16 (1 + N) bytes, at most 128 KB), -22 beyond.  probs must be free of NaN: the rank is a count
+ * of comparisons, which a NaN fails all of, so that several candidates would share a rank and some output slots stay unwritten */
 int cham_rank_items(const float* probs, const int64_t* label_next, const int64_t* neg_ids, const uint8_t* mask, int BT, int N,
                     int64_t* pred_ids, float* pred_probs, int32_t* label_rank, void* stream);
 

@@ -62,6 +62,8 @@ def _case(gpu, BT, N, C, seed=0, reps=1):
 def test_dm_fused_matches_float64_and_the_unfused_pair(gpu, BT, N, C):
     (e_o, e_dp, e_b2), (e_o2, e_dp2) = _case(gpu, BT, N, C)
     assert e_o < 2e-6 and e_dp < 5e-6 and e_b2 < 5e-6, (e_o, e_dp, e_b2)
+    # the yardstick itself (cham_gemm_f32x3 + cham_mulpred_bwd_p3) has to meet the same bounds: a wrong yardstick must not loosen the next line
+    assert e_o2 < 2e-6 and e_dp2 < 5e-6, (e_o2, e_dp2)
     # fp32-grade: not measurably worse than the on-the-fly split GEMM + the separate elementwise kernel
     assert e_o < 1.5 * e_o2 + 2e-7 and e_dp < 1.5 * e_dp2 + 5e-7, (e_o, e_o2, e_dp, e_dp2)
 
