@@ -589,7 +589,8 @@ extern "C" int cham_item_dynamic_raw(const int64_t* ids, const int64_t* ref_ts, 
     return CHAM_OK;
 }
 
-// stats from the recent-clicks population (buffer non-empty): same stats for the 3 call groups
+// stats from the recent-clicks population (buffer non-empty): same stats for the 3 call groups.  scratch: 2 * n_last floats (the raw
+// recency values, then the raw novelty values, of the population).
 extern "C" int cham_norm_stats_from_recent(const int64_t* last_ids, int n_last, int64_t max_ts, const int64_t* created,
                                            const float* pop_norm, float* scratch /*2*n_last*/, float* stats /*[3][8]*/,
                                            void* stream) {
@@ -629,7 +630,9 @@ extern "C" int cham_norm_stats_from_buffer_dev(const int64_t* buffer_ids, int n_
     return norm_stats_from_buffer_impl(buffer_ids, n_prefix, 0, created, pop_norm, scratch, stats, scalars, stream);
 }
 
-// stats from the call's own rows (empty buffer = very first batch): one group at a time
+// stats from the call's own rows (empty buffer = very first batch): one group at a time; writes stats_group[0 .. 8) only.
+// A population with no positive weight is 0 / 0 - as tf.nn.moments of an empty tensor is (nar_model.py:1078-1084 on a call whose ids
+// are all pads): the group's eight values are then NaN, nothing else is written.
 extern "C" int cham_norm_stats_from_rows(const float* rec_raw, const float* nov_raw, const float* weights, int n,
                                          float* stats_group /*[8]*/, void* stream) {
     if (!rec_raw || !nov_raw || !weights || n <= 0 || !stats_group) return -CHAM_ERR_ARG;
@@ -640,8 +643,14 @@ extern "C" int cham_norm_stats_from_rows(const float* rec_raw, const float* nov_
     return CHAM_OK;
 }
 
+// first-batch weights (nar_model.py:1078-1084).  ids half (ids != NULL, n_ids > 0): w_ids[i] = ids[i] != 0.  Slot half (neg_slot != NULL,
+// n_neg > 0): w_slots holds pmax + 1 floats, w_slots[s] = occurrences of pool slot s < pmax whose pool id is not 0; masked clicks (-1)
+// and the pad slot pmax count for nothing, so w_slots[pmax] is always 0.
 extern "C" int cham_row_weights(const int64_t* ids, int n_ids, const int32_t* neg_slot, size_t n_neg, int pmax,
                                 const int64_t* pool, float* w_ids, float* w_slots, void* stream) {
+    // a half that is asked for needs its output; the slot half also the pool and a pad slot to zero
+    if (ids && n_ids > 0 && !w_ids) return -CHAM_ERR_ARG;
+    if (neg_slot && n_neg > 0 && (!w_slots || !pool || pmax < 0)) return -CHAM_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (ids && n_ids > 0) hipLaunchKernelGGL(k_nonzero_weights, dim3((n_ids + 255) / 256), dim3(256), 0, st, ids, n_ids, w_ids);
     if (neg_slot && n_neg > 0) {

@@ -56,14 +56,20 @@ int cham_step_ints(const int64_t* ic_rows, const int64_t* ln_rows, const int64_t
 int cham_item_dynamic_raw(const int64_t* ids, const int64_t* ref_ts, int R, const int64_t* created, const float* pop_norm,
                           float* rec_raw, float* nov_raw, void* stream);
 /* normalisation population = last `recent_clicks_for_normalization` buffer clicks: nar_model.py:1062-1089, 1150-1186;
- * stats [3][8] = per call group {mean, sd, zmin, zmax} x {recency, novelty} */
+ * stats [3][8] = per call group {mean, sd, zmin, zmax} x {recency, novelty}; scratch holds 2 * n_last floats */
 int cham_norm_stats_from_recent(const int64_t* last_ids, int n_last, int64_t max_ts, const int64_t* created,
                                 const float* pop_norm, float* scratch, float* stats, void* stream);
 /* the same statistics straight from the device-resident buffer (cham_state_update): population = the valid entries among
  * the first n_prefix (= recent_clicks_for_normalization) buffer slots; scratch holds 3 * n_prefix floats */
 int cham_norm_stats_from_buffer(const int64_t* buffer_ids, int n_prefix, int64_t max_ts, const int64_t* created,
                                 const float* pop_norm, float* scratch, float* stats, void* stream);
-/* empty-buffer fallback (first batch): population = the call's own non-pad ids, nar_model.py:1078-1084, 1168-1181 */
+/* empty-buffer fallback (first batch): population = the call's own non-pad ids, nar_model.py:1078-1084, 1168-1181; weights = repetition
+ * counts, entries with weight 0 do not count; writes the 8 floats of stats_group only.  No positive weight at all is 0 / 0 (as
+ * tf.nn.moments of an empty tensor): the 8 floats are NaN.
+ * cham_row_weights makes those weights: w_ids [n_ids] = (ids != 0); w_slots [pmax + 1] = occurrences of each pool slot < pmax with a
+ * non-zero pool id among neg_slot [n_neg] (-1 = masked click and pmax = pad slot count for nothing: w_slots[pmax] is always 0).
+ * Either half may be left out (ids == NULL / neg_slot == NULL); -22 when a half that is asked for lacks its output, or the slot
+ * half its pool. */
 int cham_norm_stats_from_rows(const float* rec_raw, const float* nov_raw, const float* weights, int n, float* stats_group,
                               void* stream);
 int cham_row_weights(const int64_t* ids, int n_ids, const int32_t* neg_slot, size_t n_neg, int pmax, const int64_t* pool,

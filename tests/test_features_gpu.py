@@ -95,6 +95,52 @@ def test_item_assemble_lds_equals_elementwise(gpu, dataset, n_items, D, R):
     assert torch.equal(outs[1][0][:, ace_seg[1]:ace_seg[1] + ace_seg[2]], rt.ace.cpu()[ids.cpu()])
 
 
+@pytest.mark.parametrize("R", [7, 517, 1003])
+def test_item_assemble_float_bits_numeric_matches_float64(gpu, R):
+    """A hand-built item schema with a FLOAT-BITS numeric column (descriptor sub-field 1: the int64 metadata entry holds a float32 bit
+    pattern, values of both signs from 1e-4 to 1e4) next to an integer one - no synthetic schema has one, and `astype(float32)` of the
+    gather above would not describe it.  Both kernels against tests/features_reference.item_rows in float64: gathered columns exact, the
+    two normalised columns and the gamma / beta image within 8 x the fp32-CPU error of the same formula
+    (tests/test_features_reference_cpu.py); the two kernels bit-equal to each other; three different stats groups."""
+    from chameleon_recsys_amd import _lib
+    from chameleon_recsys_amd._lib import check
+    from tests import features_reference as FR
+    from tests.features_gpu_helpers import Out, _dev, _note, _st, _twice
+    from tests.features_reference import gpu_bounds
+    lib, k = _lib.load(), gpu_bounds()
+    inp = FR.item_inputs(R)
+    desc = inp['desc']
+    Fi = len(desc)
+    segs, singles = FR.item_segments(desc)
+    assert Fi % 4 == 0 and ((desc[:, 0] == COL_NUM) & (desc[:, 2] == 1)).sum() == 1 and ((desc[:, 0] == COL_NUM) & (desc[:, 2] == 0)).sum() == 1
+    d = {a: _dev(gpu, inp[a]) for a in ('ids', 'meta_cat', 'ace', 'rec', 'nov', 'stats', 'desc', 'params', 'gamma', 'beta')}
+    d_segs, d_singles = _dev(gpu, segs), _dev(gpu, singles)
+    P = lambda a: d[a].data_ptr()
+
+    def run(lds):
+        def go():
+            xraw, xs = Out(gpu, (R, Fi)), Out(gpu, (R, Fi))
+            if lds:
+                check(lib.cham_item_assemble_lds(P('ids'), R, inp['g1'], inp['g2'], P('meta_cat'), FR.ITEM_N, P('ace'), FR.ITEM_D, P('rec'), P('nov'), P('stats'),
+                                                 P('desc'), Fi, d_segs.data_ptr(), len(segs), d_singles.data_ptr(), len(singles), P('params'), P('gamma'),
+                                                 P('beta'), xraw.ptr(), xs.ptr(), _st()), "cham_item_assemble_lds")
+            else:
+                check(lib.cham_item_assemble(P('ids'), R, inp['g1'], inp['g2'], P('meta_cat'), FR.ITEM_N, P('ace'), FR.ITEM_D, P('rec'), P('nov'), P('stats'),
+                                             P('desc'), Fi, P('params'), P('gamma'), P('beta'), xraw.ptr(), xs.ptr(), _st()), "cham_item_assemble")
+            return xraw.numpy(), xs.numpy()
+        return _twice(go)
+    plain, tiled = run(False), run(True)
+    assert FR.same_bits(plain[0], tiled[0]) and FR.same_bits(plain[1], tiled[1]), "the two kernels differ"
+    want_raw, want_s, dyn = FR.item_rows(*FR.item_args(inp))
+    print("\nR %d Fi %d" % (R, Fi))
+    for name, (xraw, xs) in (("elementwise", plain), ("lds", tiled)):
+        assert np.array_equal(xraw[:, ~dyn].astype(np.float64), want_raw[:, ~dyn]), "%s: gathered columns differ from the reference" % name
+        _note('item.dyn ' + name, FR.rel_err(xraw[:, dyn], want_raw[:, dyn]), k['item.dyn'])
+        _note('item.xs ' + name, FR.rel_err(xs, want_s), k['item.xs'])
+    fcol = int(np.flatnonzero((desc[:, 0] == COL_NUM) & (desc[:, 2] == 1))[0])
+    assert FR.same_bits(plain[0][:, fcol], FR.float_bits_to_f32(inp['meta_cat'][3, inp['ids']])), "the float-bits column is not the stored bit pattern"
+
+
 @pytest.mark.parametrize("R,F", [(10729, 408), (4864, 72), (37, 8), (1, 4), (5000, 1024), (300, 100)])
 def test_feature_bwd_coalesced_column_sums(gpu, R, F):
     """cham_feature_bwd_ws (round 6: 64 columns x a row chunk per workgroup, coalesced row segments, partials added in a fixed order) against

@@ -147,6 +147,52 @@ def test_hip_sampler_bit_exact(gpu, B, T1, N, n_buf, buf_size, n_items, fill):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("B,T1,N,n_buf,buf_size,n_items,fill", [
+    (64, 8, 10, 100, 2000, 1000, 1500),
+    (16, 5, 4, 10, 64, 50, 0),
+])
+def test_hip_sampler_dev_equals_by_value(gpu, B, T1, N, n_buf, buf_size, n_items, fill):
+    """cham_neg_sample_dev takes the step from the step-scalars record (`which` 0: .step, 1: .step_next): all five outputs bit-equal to
+    cham_neg_sample with the same step by value, at two of the bit-exact cases above."""
+    import torch
+    from chameleon_recsys_amd import _lib
+    from chameleon_recsys_amd._lib import check, ptr
+    lib = _lib.load()
+    rng = np.random.default_rng(B * 1000 + N)
+    aci = rng.integers(1, n_items, size=(B, T1)).astype(np.int64)
+    lens = rng.integers(2, T1 + 1, size=B)
+    for b in range(B):
+        aci[b, lens[b]:] = 0
+    buf = np.zeros(buf_size, np.int64)
+    buf[:fill] = rng.integers(1, n_items, size=fill)
+    st = torch.cuda.current_stream().cuda_stream
+    rec = torch.zeros(lib.cham_step_scalars_bytes(), dtype=torch.uint8, device=gpu)
+    steps = (5, 77)
+    check(lib.cham_step_scalars_set(rec.data_ptr(), steps[0], steps[1], 0, 0.0, 0.0, 1, st), "cham_step_scalars_set")
+    d_aci, d_buf = torch.from_numpy(aci).to(gpu), torch.from_numpy(buf).to(gpu)
+    nb = lib.cham_neg_sample_workspace_bytes(B * T1, len(buf), n_buf)
+    for which in (0, 1):
+        # (outputs start as zeros, as in _gpu_sample: both forms leave pool / canon beyond the P pool entries as they were)
+        neg = torch.zeros(B, T1 - 1, N, dtype=torch.int64, device=gpu)
+        slot = torch.zeros(B, T1 - 1, N, dtype=torch.int32, device=gpu)
+        pool = torch.zeros(20 * N, dtype=torch.int64, device=gpu)
+        canon = torch.zeros(20 * N, dtype=torch.int32, device=gpu)
+        meta = torch.zeros(4, dtype=torch.int32, device=gpu)
+        ws = torch.empty(nb, dtype=torch.uint8, device=gpu)
+        check(lib.cham_neg_sample_dev(ptr(d_aci), B, T1, ptr(d_buf), len(buf), 42, rec.data_ptr(), which, 0, B, N, n_buf, ptr(neg), ptr(slot), ptr(pool),
+                                      ptr(canon), ptr(meta), ptr(ws), nb, st), "cham_neg_sample_dev")
+        torch.cuda.synchronize()
+        got = (neg.cpu().numpy(), slot.cpu().numpy(), pool.cpu().numpy(), canon.cpu().numpy(), meta.cpu().numpy())
+        want = _gpu_sample(gpu, aci, buf, N, n_buf, 42, steps[which])
+        other = _gpu_sample(gpu, aci, buf, N, n_buf, 42, steps[1 - which])
+        for name, g, w in zip(("neg_ids", "neg_slot", "pool", "canon", "meta"), got, want):
+            assert g.dtype == w.dtype and np.array_equal(g, w), (name, which)
+        assert not np.array_equal(got[0], other[0]), "the two steps draw the same negatives: `which` would not show"
+    assert lib.cham_neg_sample_dev(ptr(d_aci), B, T1, ptr(d_buf), len(buf), 42, None, 0, 0, B, N, n_buf, ptr(neg), ptr(slot), ptr(pool), ptr(canon),
+                                   ptr(meta), ptr(ws), nb, st) == -22
+
+
+@pytest.mark.gpu
 def test_hip_sampler_row_shards(gpu):
     rng = np.random.default_rng(5)
     aci = rng.integers(1, 500, size=(32, 9)).astype(np.int64)
