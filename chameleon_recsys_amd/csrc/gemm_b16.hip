@@ -422,6 +422,7 @@ extern "C" int cham_gemm_b16(const void* A, int lda, int transA, const void* B, 
     if (!nt && !tn) return -CHAM_ERR_ARG;
     if (nt && (K & 7)) return -CHAM_ERR_ARG;
     if (tn && ((M & 7) || (N & 7))) return -CHAM_ERR_ARG;
+    if (lda < (tn ? M : K) || ldb < (tn ? N : K) || ldc < N || (dref && ldr < N)) return -CHAM_ERR_ARG;      // leading dimension < the extent it strides over
     if ((size_t)lda * 2 * 256 >= WINDOW_BYTES || (size_t)ldb * 2 * 256 >= WINDOW_BYTES || (size_t)ldc * 4 * 256 >= WINDOW_BYTES ||
         (size_t)ldr * 2 * 256 >= WINDOW_BYTES)
         return -CHAM_ERR_ARG;

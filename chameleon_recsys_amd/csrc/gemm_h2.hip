@@ -904,6 +904,7 @@ static int h2_run(const void* A, long long a_plane_stride, int lda, const float*
     if ((lda & 7) || (ldb & 7) || (a_plane_stride & 7) || (b_plane_stride & 7) || (N & 3) || (ldc & 3)) return -CHAM_ERR_ARG;
     if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return -CHAM_ERR_ARG;
     if ((size_t)ldc * 4 * 256 >= WINDOW_BYTES || (size_t)ldr * 2 * 256 >= WINDOW_BYTES) return -CHAM_ERR_ARG;
+    if (lda < (tn ? M : K) || ldb < (tn ? N : K) || ldc < N || (dref_h && ldr < N)) return -CHAM_ERR_ARG;      // leading dimension < the extent it strides over
     H2Params p;
     p.A = reinterpret_cast<const _Float16*>(A); p.B = reinterpret_cast<const _Float16*>(B); p.a_ps = a_plane_stride; p.b_ps = b_plane_stride;
     p.lda = lda; p.ldb = ldb; p.sa = a_scale; p.sb = b_scale; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.bias = bias;

@@ -850,6 +850,7 @@ extern "C" int cham_gemm_p3(const void* A, long long a_plane_stride, int lda, co
     if ((lda & 7) || (ldb & 7) || (a_plane_stride & 7) || (b_plane_stride & 7) || (N & 3) || (ldc & 3)) return -CHAM_ERR_ARG;
     if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return -CHAM_ERR_ARG;
     if ((size_t)ldc * 4 * 256 >= WINDOW_BYTES || (size_t)ldr * 2 * 256 >= WINDOW_BYTES) return -CHAM_ERR_ARG;
+    if (lda < (tn ? M : K) || ldb < (tn ? N : K) || ldc < N || (dref_h && ldr < N)) return -CHAM_ERR_ARG;      // leading dimension < the extent it strides over
     P3Params p;
     p.A = reinterpret_cast<const __bf16*>(A); p.B = reinterpret_cast<const __bf16*>(B); p.a_ps = a_plane_stride; p.b_ps = b_plane_stride;
     p.lda = lda; p.ldb = ldb; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.bias = bias;
@@ -945,6 +946,7 @@ extern "C" int cham_gemm_b16_dma(const void* A, int lda, const void* B, int ldb,
     if ((lda & 7) || (ldb & 7) || (N & 3) || (ldc & 3) || (dref && (ldr & 3))) return -CHAM_ERR_ARG;
     if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)dref | (uintptr_t)bias) & 15) return -CHAM_ERR_ARG;
     if ((size_t)ldc * 4 * 256 >= WINDOW_BYTES || (size_t)ldr * 2 * 256 >= WINDOW_BYTES) return -CHAM_ERR_ARG;
+    if (lda < (tn ? M : K) || ldb < (tn ? N : K) || ldc < N || (dref && ldr < N)) return -CHAM_ERR_ARG;      // leading dimension < the extent it strides over
     P3Params p;
     p.A = reinterpret_cast<const __bf16*>(A); p.B = reinterpret_cast<const __bf16*>(B); p.a_ps = 0; p.b_ps = 0;
     p.lda = lda; p.ldb = ldb; p.C = reinterpret_cast<float*>(C); p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.bias = bias;

@@ -352,6 +352,9 @@ static inline int gemm_plan(GemmParams& p, const float* A, int lda, int transA, 
     if (!transB && (N & 3)) return -CHAM_ERR_ARG;        // B[K,N] row-major
     if (transB && (K & 3)) return -CHAM_ERR_ARG;         // B stored [N,K]
     if (rowscale && ((ldrs & 3) || rs_div <= 0)) return -CHAM_ERR_ARG;
+    // a leading dimension is never smaller than the extent it strides over (with ldc < N the rows of C would overwrite each other)
+    if (lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N || (dref && ldr < N) || (rowscale && ldrs < (transA ? M : K)))
+        return -CHAM_ERR_ARG;
     // tile windows address 2^31 bytes with 32-bit offsets: a 256-row (or 32-k-row) slab of any operand must fit
     if ((size_t)lda * 4 * 256 >= WINDOW_BYTES || (size_t)ldb * 4 * 256 >= WINDOW_BYTES || (size_t)ldc * 4 * 256 >= WINDOW_BYTES ||
         (size_t)ldr * 4 * 256 >= WINDOW_BYTES)

@@ -135,7 +135,21 @@ int cham_dense_rows(const float* Xc_s, int Fc, const float* Xi_s, int Fi, int BT
 /* --- K2/K4 fp32 MFMA GEMM with fused prologue/epilogue: tf.layers.Dense at nar_model.py:374-405, 410-426, 447-473,
  * the RNN input projection (:1308-1361) and their gradients.
  * C[M,N] (+)= epi(op(A)[M,K] * op(B)[K,N]); transA: A stored [K,M]; transB: B stored [N,K];
- * epi: +bias, act; or *act'(dref) (dgrad); rowscale: A_stored[r,c] *= rowscale[(r / rs_div), c] */
+ * epi: +bias, act; or *act'(dref) (dgrad); rowscale: A_stored[r,c] *= rowscale[(r / rs_div), c]
+ * Argument rules (-22 otherwise; shared by cham_gemm_bf16, cham_gemm_f32x3 and cham_gemm_f32x2h):
+ *   - M > 0, N > 0, K >= 0.  K == 0 is the empty sum: C = epi(bias), and C is left as it is under accumulate.
+ *   - lda % 4 == 0, ldb % 4 == 0, and the contiguous extent of each operand % 4 == 0: K for A [M, K] and for B stored [N, K], M for A
+ *     stored [K, M], N for B [K, N]; with a rowscale: ldrs % 4 == 0 and rs_div > 0 (rs_div need not divide the rows: the last group is
+ *     partial).  N % 4 != 0 is possible with transB only.
+ *   - a leading dimension is at least the extent it strides over: lda >= (transA ? M : K), ldb >= (transB ? K : N), ldc >= N, ldr >= N when
+ *     dref is given, ldrs >= (transA ? M : K) when rowscale is given.  Operands may be views: larger leading dimensions, bases at a column
+ *     offset (A, B and rowscale 16-byte aligned); what lies between the rows is neither read into a result nor written.
+ *   - ldc, ldr and the alignment of C and dref are free (4-byte elements): ldc % 4 != 0 or a C that is not 16-byte aligned only sends the
+ *     split-K reduction down its scalar branch.
+ *   - 256 rows of any operand span less than 2^31 bytes.
+ *   - epilogues per form: NN + bias (+ leaky | tanh), rowscale only with bias + leaky; NT plain | x act'(dref), accumulate allowed; TN plain,
+ *     accumulate, rowscale, K-splits (splits_hint 1 none, 0 automatic, n at most n; `workspace` holds splits x M x N floats; a bias is
+ *     added once, by the reduction).  transA with transB does not occur. */
 int cham_gemm_f32(const float* A, int lda, int transA, const float* B, int ldb, int transB, float* C, int ldc, int M, int N,
                   int K, const float* bias, int act, const float* dref, int ldr, int dact, const float* rowscale, int ldrs,
                   int rs_div, int accumulate, float* workspace, size_t workspace_bytes, int splits_hint, void* stream);
@@ -180,8 +194,11 @@ int cham_gemm_f32x2h(const float* A, int lda, int transA, const float* B, int ld
  *     x leaky'(saved activation) with dref_h = the h plane [M, ldr] of that activation and dact = CHAM_ACT_LEAKY.
  *   tn = 1 (TN): A stored [K, lda >= M], B stored [K, ldb >= N]; M % 256 == 0, N % 256 == 0, any K; split-K through `workspace`
  *     (splits_hint: 1 none, 0 automatic, n at most n; fixed-order reduction); accumulate adds to C.
- * Returns -EINVAL for a shape it does not take (the caller keeps cham_gemm_f32x3 for those).  Leading dimensions and plane strides
- * % 8 == 0, 16-byte aligned bases.  cham_gemm_p3_launch_counts: out8[0] / out8[1] = NT / TN launches since the last reset, out8[6] /
+ * Returns -EINVAL for a shape it does not take (the caller keeps cham_gemm_f32x3 for those), K <= 0 included.  Leading dimensions and plane
+ * strides % 8 == 0 (ldc % 4 == 0), 16-byte aligned bases; lda >= K and ldb >= K (NT) / lda >= M and ldb >= N (TN), ldc >= N, ldr >= N when
+ * dref_h is given: -EINVAL otherwise.  cham_gemm_b16_dma, cham_gemm_h2, cham_gemm_h2b and cham_gemm_h2_dgrad_gs keep the same rules,
+ * K <= 0 included.
+ * cham_gemm_p3_launch_counts: out8[0] / out8[1] = NT / TN launches since the last reset, out8[6] /
  * out8[7] = epilogue variant / K-splits of the last launch. */
 int cham_gemm_p3(const void* A, long long a_plane_stride, int lda, const void* B, long long b_plane_stride, int ldb, int tn, float* C,
                  int ldc, int M, int N, int K, const float* bias, int act, const void* dref_h, int ldr, int dact, int accumulate,
@@ -309,7 +326,8 @@ int cham_dm_mulpred_p3(const float* dS1, int lds1, int K, const void* Wp, long l
  *     epilogue + bias (fp32) and act, or x act'(dref) with dref = the saved bf16 activation [M, ldr] (dgrad, bf16 out);
  *   transA = 1, transB = 0 (TN): A stored [K, lda >= M], B stored [K, ldb >= N] bf16; C fp32 (+)=; split-K through `workspace`
  *     (splits_hint 1 = none, 0 = automatic; fixed-order reduction).
- * K % 8 == 0 (NT), M % 8 == 0 and N % 8 == 0 (TN), N % 4 == 0, leading dimensions % 8 == 0, 16-byte aligned bases. */
+ * K > 0, K % 8 == 0 (NT), M % 8 == 0 and N % 8 == 0 (TN), N % 4 == 0, lda and ldb % 8 == 0, ldc and ldr % 4 == 0, 16-byte aligned bases; lda >= K
+ * and ldb >= K (NT) / lda >= M and ldb >= N (TN), ldc >= N, ldr >= N when dref is given; -EINVAL otherwise. */
 int cham_gemm_b16(const void* A, int lda, int transA, const void* B, int ldb, int transB, void* C, int ldc, int out_f32, int M,
                   int N, int K, const float* bias, int act, const void* dref, int ldr, int dact, int accumulate, float* workspace,
                   size_t workspace_bytes, int splits_hint, void* stream);

@@ -6,25 +6,7 @@ product whose error against float64 is of the native fp32 MFMA's class - half th
 import numpy as np
 import pytest
 
-
-def h2_scale(bound):
-    """h2_finish_scale: bound = m 2^e (0.5 <= m < 1) -> scale = 2^(15 - e), so that bound * scale lies in [2^14, 2^15)."""
-    if not (bound > 0 and np.isfinite(bound)):
-        return 1.0
-    _, e = np.frexp(np.float32(bound))
-    k = int(np.clip(15 - int(e), -110, 110))
-    return float(np.ldexp(1.0, k))
-
-
-def split2h(x, scale):
-    xs = (np.asarray(x, np.float32) * np.float32(scale)).astype(np.float32)          # exact (power of two) unless it leaves the fp32 range
-    with np.errstate(over='ignore'):
-        h = xs.astype(np.float16)
-    r = (xs - h.astype(np.float32)).astype(np.float32)                              # exact in fp32
-    l = r.astype(np.float16)
-    hb = h.view(np.uint16).copy()
-    hb[(np.asarray(x) > 0) & (hb == 0)] = 1                                         # h2_keep_sign: a positive value never stores +0
-    return hb.view(np.float16), l
+from tests.gemm_reference import h2_scale, split2h          # the numpy models live there (shared with the GEMM reference)
 
 
 def test_scale_rule_puts_the_bound_below_2_15():

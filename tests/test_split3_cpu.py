@@ -5,21 +5,7 @@ accumulation step."""
 import numpy as np
 import pytest
 
-
-def bf16_rne(x):
-    """float32 -> nearest bf16 (ties to even), returned as float32 (what v_cvt_pk_bf16_f32 does for finite inputs)."""
-    u = np.asarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    r = u + 0x7FFF + ((u >> 16) & 1)
-    return ((r >> 16) << 16).astype(np.uint32).view(np.float32)
-
-
-def split3(a):
-    a = np.asarray(a, np.float32)
-    h = bf16_rne(a)
-    r = (a - h).astype(np.float32)          # exact in fp32 (Sterbenz-like: |r| <= 2^-8 |a|, fits 16 bits of significand)
-    m = bf16_rne(r)
-    r2 = (r - m).astype(np.float32)
-    return h, m, bf16_rne(r2)
+from tests.gemm_reference import bf16_rne, split3          # the numpy models live there (shared with the GEMM reference)
 
 
 def test_three_bf16_planes_sum_to_the_fp32_value_exactly():
