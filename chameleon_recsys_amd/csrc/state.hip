@@ -61,7 +61,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_state_buffer_update(
     if ((tid & 63) == 0) smin[tid >> 6] = mn;
     int nb;
     const int pre = block_exclusive_scan(cnt, sh, &nb);     // (barriers inside also publish smin)
-    if (nb == 0) return;                                    // no click in the batch: state unchanged (uniform exit)
+    // no click in the batch: state unchanged (uniform exit).  cham_state_update still rebuilds recent_pop from the unchanged buffer, and
+    // k_state_hist ADDS to n_valid[1]: re-arm it here as the regular exit does, or the denominator of pop_norm doubles
+    if (nb == 0) { if (tid == 0) n_valid[1] = 0; return; }
     for (int i = 0; i < ST_THREADS / 64; ++i) mn = smin[i] < mn ? smin[i] : mn;
     const long long thr = mn - hours_ms;                    // :225-228
     // reversed batch clicks first (:212): the j-th non-padding click (row-major order) lands at nb-1-j

@@ -9,6 +9,8 @@ Pinned against the reference class itself: tests/golden/state_trace.npz (oracle/
 """
 import numpy as np
 
+MILISECS_BY_HOUR = 1000 * 60 * 60         # grouped as in clicked_items_state.py:226: hours * 1000 * 60 * 60 rounds differently (0.009 h)
+
 
 def batch_clicks_for_state(item_clicked, label_last_item, event_timestamp):
     """nar_model.py:1635-1646.  Returns (ids_nonzero, ts_nonzero), row-major order."""
@@ -40,7 +42,7 @@ class ClickedItemsStateOracle:
     def update_items_state(self, ids, ts):
         # clicked_items_state.py:206-223
         batch = np.hstack([ids.reshape(-1, 1), ts.reshape(-1, 1)])[::-1]
-        thr = np.min(ts) - int(self.hours * 1000 * 60 * 60)            # :225-228
+        thr = np.min(ts) - int(self.hours * MILISECS_BY_HOUR)          # :225-228
         kept = self.buffer[self.buffer[:, 1] >= thr]
         buf = np.vstack([batch, kept])[: self.max_size]
         if buf.shape[0] < self.max_size:

@@ -233,3 +233,199 @@ def test_hip_sampler_nearly_empty_buffer_falls_back_to_full_select(gpu):
     P = len(aux['pool'])
     assert meta[3] == P and meta[1] == len(aux['buf_sample']) == 40
     assert np.array_equal(pool[:P], aux['pool']) and np.array_equal(neg, ref)
+
+
+# ---- the sampler at its structural edges: every output bit-exact against the oracle ---------------------------------------------------
+def _gpu_sample_raw(gpu, aci, buf, N, n_buf, seed, step, row_begin=0, row_count=None, ws_short=0, fill=-5):
+    """cham_neg_sample over outputs prefilled with `fill`; returns (rc, neg, slot, pool, canon, meta) - flat arrays, never NULL pointers."""
+    import torch
+    from chameleon_recsys_amd import _lib
+    from chameleon_recsys_amd._lib import ptr
+    lib = _lib.load()
+    Bg, T1 = aci.shape
+    row_count = Bg if row_count is None else row_count
+    n_out = max(1, row_count * max(T1 - 1, 0) * max(N, 0))
+    d_aci = torch.from_numpy(aci).to(gpu); d_buf = torch.from_numpy(buf).to(gpu)
+    neg = torch.full((n_out,), fill, dtype=torch.int64, device=gpu)
+    slot = torch.full((n_out,), fill, dtype=torch.int32, device=gpu)
+    pool = torch.full((max(1, 20 * N),), fill, dtype=torch.int64, device=gpu)
+    canon = torch.full((max(1, 20 * N),), fill, dtype=torch.int32, device=gpu)
+    meta = torch.full((4,), fill, dtype=torch.int32, device=gpu)
+    nb = lib.cham_neg_sample_workspace_bytes(Bg * T1, len(buf), n_buf)
+    ws = torch.empty(nb, dtype=torch.uint8, device=gpu)
+    rc = lib.cham_neg_sample(ptr(d_aci), Bg, T1, ptr(d_buf), len(buf), seed, step, row_begin, row_count, N, n_buf, ptr(neg), ptr(slot), ptr(pool),
+                             ptr(canon), ptr(meta), ptr(ws), nb - ws_short, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return (rc,) + tuple(t.cpu().numpy() for t in (neg, slot, pool, canon, meta))
+
+
+def _assert_equals_oracle(gpu, aci, buf, N, n_buf, seed=42, step=3, row_begin=0, row_count=None):
+    """neg_ids, pool, canon and meta equal the oracle's, bit for bit, over prefilled outputs; the slots name the sampled ids.
+    Returns (neg [rows, T, N], slot, aux)."""
+    Bg, T1 = aci.shape
+    row_count = Bg if row_count is None else row_count
+    rc, neg, slot, pool, canon, meta = _gpu_sample_raw(gpu, aci, buf, N, n_buf, seed, step, row_begin, row_count)
+    assert rc == 0
+    ref, aux = S.batch_negative_samples(aci, buf, N, n_buf, seed, step, rows=range(row_begin, row_begin + row_count), return_aux=True)
+    P, pmax = len(aux['pool']), 20 * N
+    assert meta.tolist() == [0, len(aux['buf_sample']), 0, P]
+    assert np.array_equal(pool[:P], aux['pool']) and not pool[P:].any()
+    assert np.array_equal(canon[:P], aux['canon']) and np.array_equal(canon[P:], np.arange(P, pmax))
+    if row_count == 0:
+        return None, None, aux
+    neg, slot = neg.reshape(ref.shape), slot.reshape(ref.shape)
+    assert np.array_equal(neg, ref)
+    ok = (slot >= 0) & (slot < pmax)
+    assert np.array_equal(pool[np.where(ok, slot, 0)][ok], neg[ok])
+    assert (neg[slot == pmax] == 0).all() and (neg[slot < 0] == 0).all() and ((slot >= -1) & (slot <= pmax)).all()
+    assert np.array_equal(slot[ok], aux['slots'][ok]) and np.array_equal(ok, aux['slots'] >= 0)
+    pad = np.repeat((aci[row_begin:row_begin + row_count, :-1] == 0)[:, :, None], N, 2)
+    assert (slot[pad] == -1).all() and (slot[~pad & ~ok] == pmax).all()          # padded click: -1; too few candidates: the pad slot
+    return neg, slot, aux
+
+
+def _ragged(rng, B, T1, n_items):
+    aci = rng.integers(1, n_items, size=(B, T1)).astype(np.int64)
+    for b, L in enumerate(rng.integers(1, T1 + 1, size=B)):
+        aci[b, L:] = 0
+    return aci
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fill", [300, 0])
+def test_hip_sampler_without_buffer_sample(gpu, fill):
+    """n_from_buffer = 0 (a zero-length sample slot array in the workspace): the pool is the batch alone, whatever the buffer holds."""
+    rng = np.random.default_rng(20 + fill)
+    aci = _ragged(rng, 12, 7, 400)
+    buf = np.zeros(400, np.int64); buf[:fill] = rng.integers(1, 400, size=fill)
+    _, _, aux = _assert_equals_oracle(gpu, aci, buf, 6, 0)
+    assert len(aux['buf_sample']) == 0 and np.isin(aux['pool'], aci).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("buf_size", [255, 256, 257, 2048, 2049])
+def test_hip_sampler_buffer_sizes_at_the_block_and_tile_edges(gpu, buf_size):
+    """One element less / more than a block of 256 keys and than the 2048-key LDS tile of the rank count; the last buffer slot is live."""
+    rng = np.random.default_rng(buf_size)
+    aci = _ragged(rng, 10, 6, 900)
+    buf = rng.integers(1, 900, size=buf_size).astype(np.int64)
+    buf[rng.random(buf_size) < 0.1] = 0
+    buf[-1], buf[0] = 77, 78
+    _assert_equals_oracle(gpu, aci, buf, 7, 120)
+
+
+@pytest.mark.gpu
+def test_hip_sampler_session_that_covers_the_pool(gpu):
+    """A session that holds every distinct id of the pool has no candidate: its valid clicks get N zeros with the pad slot 20 N; its
+    padded click gets slot -1."""
+    aci = np.array([[1, 2, 3, 4, 5, 0, 0], [2, 3, 0, 0, 0, 0, 0], [5, 5, 4, 0, 0, 0, 0]], dtype=np.int64)
+    buf = np.array([3, 4, 0, 5, 1, 0, 0, 2], dtype=np.int64)
+    N = 4
+    neg, slot, aux = _assert_equals_oracle(gpu, aci, buf, N, 6)
+    assert set(aux['pool'].tolist()) == {1, 2, 3, 4, 5}
+    assert not neg[0].any() and (slot[0, :5] == 20 * N).all() and (slot[0, 5] == -1).all()      # (the output drops position 6)
+    assert (np.count_nonzero(neg[1, :2], axis=1) == 3).all() and (np.count_nonzero(neg[2, :3], axis=1) == 3).all()
+
+
+@pytest.mark.gpu
+def test_hip_sampler_pool_of_one_repeated_id(gpu):
+    """Every pool entry is the same id: canon is all zeros; sessions that hold the id get nothing, and with a second id in the batch the
+    sessions of that id get the first one once, then zeros."""
+    aci = np.full((4, 5), 7, np.int64); aci[2, 3:] = 0
+    buf = np.full(40, 7, np.int64)
+    neg, slot, aux = _assert_equals_oracle(gpu, aci, buf, 3, 25)
+    assert not aux['canon'].any() and len(aux['pool']) == 18 + 25 and not neg.any()
+    buf[:] = 0
+    aci[1] = [9, 9, 9, 0, 0]; aci[3] = [9, 0, 0, 0, 0]
+    neg, slot, aux = _assert_equals_oracle(gpu, aci, buf, 3, 25)
+    assert neg[1, :3].tolist() == [[7, 0, 0]] * 3 and neg[3, 0].tolist() == [7, 0, 0] and neg[0].tolist() == [[9, 0, 0]] * 4
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_distinct", [6, 5])
+def test_hip_sampler_exactly_enough_and_one_too_few_candidates(gpu, n_distinct):
+    """N = 6 negatives from exactly 6 distinct candidates (no zero) and from 5 (one trailing zero, pad slot)."""
+    N = 6
+    aci = np.array([[1, 2, 1], [2, 1, 0], [1, 2, 2], [2, 2, 1]], dtype=np.int64)
+    buf = np.zeros(20, np.int64)
+    buf[:2 * n_distinct] = np.tile(np.arange(101, 101 + n_distinct), 2)
+    neg, slot, aux = _assert_equals_oracle(gpu, aci, buf, N, 16)
+    valid = aci[:, :-1] != 0
+    assert (np.count_nonzero(neg[valid], axis=1) == n_distinct).all()
+    assert all(sorted(r[:n_distinct].tolist()) == list(range(101, 101 + n_distinct)) for r in neg[valid])
+    assert (slot[valid][:, n_distinct:] == 20 * N).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which,limit", [("buffer", 101), ("buffer", 100), ("pool", 100)])
+@pytest.mark.parametrize("nv_case", ["at", "above", "three_times"])
+def test_hip_sampler_prefilter_switch(gpu, which, limit, nv_case):
+    """k_sel_threshold prefilters iff #valid keys > 1.5 limit + 64: #valid = floor of that (full rank-select), one more (prefilter with a
+    threshold of almost 2^32) and three times as many, for the buffer selection (limit = n_from_buffer, odd and even) and the pool
+    selection (limit = 20 N)."""
+    want = int(1.5 * limit + 64)
+    nv = {"at": want, "above": want + 1, "three_times": 3 * want}[nv_case]
+    rng = np.random.default_rng(nv + limit)
+    if which == "buffer":
+        N, n_buf = 5, limit
+        aci = _ragged(rng, 6, 5, 3000)
+        buf = np.zeros(800, np.int64)
+        buf[rng.permutation(800)[:nv]] = rng.integers(1, 3000, size=nv)
+        assert np.count_nonzero(buf) == nv
+    else:
+        N, n_buf = limit // 20, 10
+        buf = np.zeros(64, np.int64); buf[5:15] = rng.integers(1, 3000, size=10)
+        B, T1 = 40, 20
+        aci = np.zeros((B, T1), np.int64)
+        left = nv - 10                                     # valid keys of the pool selection = batch clicks + the 10 sampled buffer ids
+        for b in range(B):
+            L = min(T1, left, int(rng.integers(T1 - 3, T1 + 1)))
+            aci[b, :L] = rng.integers(1, 3000, size=L)
+            left -= L
+        assert left == 0 and np.count_nonzero(aci) == nv - 10
+    _, _, aux = _assert_equals_oracle(gpu, aci, buf, N, n_buf, row_count=6)
+    assert len(aux['buf_sample']) == min(n_buf, np.count_nonzero(buf)) and len(aux['pool']) == 20 * N
+
+
+@pytest.mark.gpu
+def test_hip_sampler_shortest_session_and_single_negative(gpu):
+    """T1 = 2 (one click and its label) and N = 1."""
+    rng = np.random.default_rng(8)
+    buf = rng.integers(1, 200, size=300).astype(np.int64)
+    aci = rng.integers(1, 200, size=(9, 2)).astype(np.int64); aci[4, 1] = 0; aci[7] = 0
+    _assert_equals_oracle(gpu, aci, buf, 5, 40)
+    _assert_equals_oracle(gpu, _ragged(rng, 9, 6, 200), buf, 1, 40)
+    _assert_equals_oracle(gpu, aci, buf, 1, 0)
+
+
+@pytest.mark.gpu
+def test_hip_sampler_largest_pool_that_fits_lds(gpu):
+    """N = 819: 20 N = 16380 pool slots, sorted as 16384 keys in 128 KB of LDS - the largest N the click kernel takes.  N = 820 doubles the
+    sort to 32768 keys, past the LDS budget: -22 and nothing written."""
+    rng = np.random.default_rng(819)
+    aci = np.array([[11, 12, 13], [14, 15, 0]], dtype=np.int64)
+    buf = rng.integers(1, 46000, size=20000).astype(np.int64)
+    neg, slot, aux = _assert_equals_oracle(gpu, aci, buf, 819, 17000)
+    assert len(aux['pool']) == 16380 and len(aux['buf_sample']) == 17000 and np.count_nonzero(neg[0, 0]) == 819
+    rc, neg, slot, pool, canon, meta = _gpu_sample_raw(gpu, aci, buf, 820, 17000, 42, 3)
+    assert rc == -22 and (neg == -5).all() and (slot == -5).all() and (pool == -5).all() and (meta == -5).all()
+
+
+@pytest.mark.gpu
+def test_hip_sampler_argument_errors_and_empty_row_range(gpu):
+    """row_count = 0 is not an error: pool, canon and meta are written (another rank's rows are sampled from the same pool), neg_ids is not.
+    A row range past the batch, T1 = 1, N = 0 and a workspace one byte short are -22 with every output as it was."""
+    rng = np.random.default_rng(9)
+    aci = _ragged(rng, 8, 5, 300)
+    buf = rng.integers(1, 300, size=500).astype(np.int64)
+    _assert_equals_oracle(gpu, aci, buf, 4, 50, row_begin=3, row_count=0)
+    _assert_equals_oracle(gpu, aci, buf, 4, 50, row_begin=8, row_count=0)
+    rc, neg = _gpu_sample_raw(gpu, aci, buf, 4, 50, 42, 3, 3, 0)[:2]
+    assert rc == 0 and (neg == -5).all()
+    _assert_equals_oracle(gpu, aci, buf, 4, 50, row_begin=5, row_count=3)
+    untouched = lambda out: out[0] == -22 and all((a == -5).all() for a in out[1:])
+    assert untouched(_gpu_sample_raw(gpu, aci, buf, 4, 50, 42, 3, 5, 4))              # rows 5 .. 8 of 8
+    assert untouched(_gpu_sample_raw(gpu, aci, buf, 4, 50, 42, 3, 9, 0))
+    assert untouched(_gpu_sample_raw(gpu, aci[:, :1].copy(), buf, 4, 50, 42, 3))       # T1 = 1
+    assert untouched(_gpu_sample_raw(gpu, aci, buf, 0, 50, 42, 3))                     # N = 0
+    assert untouched(_gpu_sample_raw(gpu, aci, buf, 4, 50, 42, 3, ws_short=1))
