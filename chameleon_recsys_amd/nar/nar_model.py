@@ -9,6 +9,8 @@ Mirrors nar_module/nar/nar_model.py of the reference:
 PyTorch is only used for device memory, streams and (data-parallel) torch.distributed; all arithmetic of the step
 runs in the hand-written HIP kernels.  There is no CPU fallback.
 """
+import contextlib
+import ctypes
 import math
 import os
 
@@ -18,11 +20,11 @@ import torch
 from .. import _lib
 from .. import _roctx
 from .._lib import check, ptr
+from .candidate_rows import (ACT_LEAKY, ACT_NONE, ACT_TANH, Bf16Rows, F32Rows, H2Rows, P3Rows, blocked_plane_elements,  # noqa: F401
+                             planes_from_blocked, planes_to_blocked)
 from .clicked_items_state import lane_stream
 from .layout import COL_ITEMEMB, ParamLayout
 from .metrics import BEYOND_ACCURACY_PER_CLICK, ItemCoverage
-
-ACT_NONE, ACT_LEAKY, ACT_TANH = 0, 1, 2
 
 
 class ModeKeys:                       # tf.estimator.ModeKeys
@@ -154,6 +156,7 @@ class NARRuntime:
     """Everything that outlives a single train()/evaluate() call: weights + Adam slots in ONE flat HBM buffer,
     resident article tables (ACE matrix, metadata - re-fed from numpy every step by the reference,
     nar_model.py:1458-1467), global step, workspaces."""
+    plans_created = 0         # plans built by plan() (bookkeeping: a first-seen padded length costs GBs of allocation)
 
     def __init__(self, params, device='cuda:0', seed=42, weights=None):
         self.lib = _lib.load()
@@ -312,35 +315,19 @@ class NARRuntime:
         # whenever the fp32 master copy changed (csrc/gemm_b16.hip wants both operands k-contiguous: W^T forward, W dgrad)
         self.b16 = self.gemm_dtype == 'bf16'
         self.shadow, self._shadow_key, self.weights_version = {}, None, 0
-        if self.b16:
-            if L.C % 128:
-                raise ValueError("gemm_dtype='bf16' needs CAR_embedding_size % 128 == 0")
-            for name in ('W2', 'Ws1', 'Ws2', 'Ws3'):
-                r, c = L.entries[name].shape
-                self.shadow[name] = torch.zeros(r, c, dtype=torch.bfloat16, device=dev)
-                self.shadow[name + 'T'] = torch.zeros(c, r, dtype=torch.bfloat16, device=dev)
         # bf16 configuration: the three candidate-row CAR GEMMs on the LDS-DMA core (csrc/gemm_p3.hip, gemm_b1_kernel) where it takes the
         # shape; the register-staged kernels of csrc/gemm_b16.hip otherwise (tests switch rt.b16_dma off to cover those at the G1 shape)
         self.b16_dma = self.gemm_dtype == 'bf16' and L.C % 256 == 0
         # ... and the scorer layer-1 dgrad fused with the cand (.) pred / CAR-tanh backward (csrc/dm_fused.hip, MODE 2) where the kernel takes
         # the shape (1 + N in [32, 256] is checked per step)
         self.dm_fused_b16 = self.gemm_dtype == 'bf16' and L.entries['Ws1'].shape == (L.C, 128) and L.C % 64 == 0
-        if self.p3:
-            C_ = L.C
-            npl, pdt = (2, torch.float16) if self.h2 else (3, torch.bfloat16)
-            self.w2p = torch.zeros(npl, C_, C_, dtype=pdt, device=dev)       # planes of W2 as stored (CAR dgrad)
-            self.w2tp = torch.zeros(npl, C_, C_, dtype=pdt, device=dev)      # planes of W2^T (CAR forward)
-            if self.h2:      # H2Scale records (32 bytes each, zero-initialised): W2's scale; max row norm of Ws1 (factor of the dZ2 bound)
-                self.sc_w2 = torch.zeros(8, dtype=torch.float32, device=dev)
-                self.sc_ws1n = torch.zeros(8, dtype=torch.float32, device=dev)
-                # constant record of an operand bounded by 1 (cand (.) pred: tanh x tanh): scale 2^14 - a factor of two inside fp16's range
-                self.sc_unit = torch.tensor([16384.0, 1.0 / 16384.0, 1.0, 0, 0, 0, 0, 0], dtype=torch.float32, device=dev)
-            # scorer layer-1 dgrad fused with the cand (.) pred backward (csrc/dm_fused.hip) where the kernel takes the shape; otherwise
-            # (and for 1 + N outside [32, 256]) the two separate kernels
-            self.dm_fused = L.entries['Ws1'].shape == (C_, 128) and C_ % 64 == 0
-            self.ws1p = torch.zeros(3, C_, 128, dtype=torch.bfloat16, device=dev)     # planes of Ws1 as stored
-            if self.h2:       # ... and its two fp16 planes under the scale of sc_ws1n (the fused dgrad's own products, CHAM_S1_H2)
-                self.ws1h = torch.zeros(2, C_, 128, dtype=torch.float16, device=dev)
+        # plane arms: scorer layer-1 dgrad fused with the cand (.) pred backward (csrc/dm_fused.hip) where the kernel takes the shape; otherwise
+        # (and for 1 + N outside [32, 256]) the two separate kernels
+        self.dm_fused = self.p3 and L.entries['Ws1'].shape == (L.C, 128) and L.C % 64 == 0
+        # The arithmetic of the candidate rows (nar/candidate_rows.py): the arm the switches above select - it allocates its weight planes / shadows
+        # and scale records here, as attributes of this runtime - and the fp32 rows every step falls back to that the planes do not take
+        self.f32_rows = F32Rows(self)
+        self.arm = Bf16Rows(self) if self.b16 else (H2Rows if self.h2 else P3Rows)(self) if self.p3 else self.f32_rows
         self._plans = {}
         self.max_plans = 24                       # padded lengths T seen in a run (seq_len - 1 = 19 at most for G1)
         self.plan_bytes_budget = 128 << 30        # of the 288 GB: activations of the cached shapes
@@ -380,33 +367,18 @@ class NARRuntime:
     def shadows_stale(self):
         return (self.b16 or self.p3) and (self.global_step, self.weights_version) != self._shadow_key
 
+    def step_arm(self, planes=True):
+        # the arm of a step or a plan: the configured one, or the fp32 rows where planes cannot be used - planes=False: dropout, no candidate
+        # row; rt.p3 switched off on the live runtime (bench.py's native-MFMA leg)
+        return self.arm if (self.b16 or (self.p3 and planes)) else self.f32_rows
+
     def refresh_shadows(self):
         """bf16 shadows (bf16 configuration) / bf16 plane shadows of W2 (plane-resident CAR GEMMs) of the candidate-row GEMM weights,
         once per weight version (one small launch per weight)."""
         if not self.shadows_stale():
             return
         key = (self.global_step, self.weights_version)
-        if self.h2:
-            C = self.layout.C
-            check(self.lib.cham_split2h(ptr(self.p('W2')), C, C, C, ptr(self.w2p), C * C, C, ptr(self.w2tp), C * C, C, ptr(self.sc_w2), 1, _stream()),
-                  "cham_split2h")
-            k1 = self.layout.entries['Ws1'].shape[1]
-            check(self.lib.cham_h2_scale_rownorm(ptr(self.p('Ws1')), C, k1, k1, None, ptr(self.sc_ws1n), _stream()), "cham_h2_scale_rownorm")
-        elif self.p3:
-            C = self.layout.C
-            check(self.lib.cham_split3(ptr(self.p('W2')), C, C, C, ptr(self.w2p), C * C, C, ptr(self.w2tp), C * C, C, _stream()), "cham_split3")
-        if self.p3:
-            C = self.layout.C
-            if self.dm_fused:
-                check(self.lib.cham_split3(ptr(self.p('Ws1')), C, 128, 128, ptr(self.ws1p), C * 128, 128, None, 0, 0, _stream()), "cham_split3")
-                if self.dm_f16:     # (scale: the row-norm record derived just above - no second pass over the weight)
-                    check(self.lib.cham_split2h(ptr(self.p('Ws1')), C, 128, 128, ptr(self.ws1h), C * 128, 128, None, 0, 0, ptr(self.sc_ws1n), 0,
-                                                _stream()), "cham_split2h")
-        if self.b16:
-            for name in ('W2', 'Ws1', 'Ws2', 'Ws3'):
-                r, c = self.layout.entries[name].shape
-                check(self.lib.cham_cast_b16(ptr(self.p(name)), r, c, ptr(self.shadow[name]), ptr(self.shadow[name + 'T']), _stream()),
-                      "cham_cast_b16")
+        self.arm.refresh_shadows(_stream())
         self._shadow_key = key
 
     def state_dict(self):
@@ -455,7 +427,7 @@ class NARRuntime:
                 self._plans.pop(next(iter(self._plans)))          # oldest entry (dicts keep insertion order)
             pl = StepPlan(self, B, T, N, n_buf, Bg or B)
             pl.nbytes = pl.allocated_bytes()                       # what the eviction above counts for the plans already cached
-            self.plans_created = getattr(self, 'plans_created', 0) + 1      # (bookkeeping: a first-seen padded length costs GBs of allocation)
+            self.plans_created += 1
         self._plans[key] = pl                                      # (re)insert as most recently used
         return pl
 
@@ -476,151 +448,76 @@ class NARRuntime:
             self.plan(B, int(T), N, n_buf, Bg)
 
     # ---- thin kernel wrappers -------------------------------------------------------------------------
+    def _timed(self, splits, counters, record):
+        return _TimedLaunch(self, splits, counters, record)
+
     def gemm(self, A, B, C, M, N, K, lda, ldb, ldc, transA=0, transB=0, bias=None, act=ACT_NONE, dref=None, ldr=0,
              dact=ACT_NONE, rowscale=None, ldrs=0, rs_div=1, accumulate=0, splits=1, force_f32=False, h2scales=None):
         """h2scales = (record of A [x rowscale], record of B): the two-fp16-plane form of the bf16x3 kernel (cham_gemm_f32x2h; default
         arithmetic only - the other arithmetics ignore it)."""
-        ws = None
-        if splits != 1:
-            ws = self._lane_ws('gemm_ws')
-        prof = self.profile
         bf16 = self.gemm_dtype == 'bf16' and not force_f32
         x3 = self.x3 and not force_f32
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            c0 = self._tile_counts()
-            x0 = self._tile_counts_x3() if x3 else None
-            e0.record()       # torch's current stream == the stream the kernel is launched on (_stream())
-        x2h = h2scales is not None and x3 and not bf16 and self.s1_h2
-        if x2h:
-            if dref is not None or transB:
-                raise ValueError("the two-plane form takes the NN and TN shapes only")
-            check(self.lib.cham_gemm_f32x2h(ptr(A), lda, transA, ptr(B), ldb, transB, ptr(C), ldc, M, N, K, ptr(bias), act, ptr(rowscale), ldrs,
-                                            rs_div, accumulate, ptr(ws), ws.numel() * 4 if ws is not None else 0, splits, ptr(h2scales[0]),
-                                            ptr(h2scales[1]), _stream()), "cham_gemm_f32x2h")
-        else:
-            fn = self.lib.cham_gemm_bf16 if bf16 else (self.lib.cham_gemm_f32x3 if x3 else self.lib.cham_gemm_f32)
-            check(fn(ptr(A), lda, transA, ptr(B), ldb, transB, ptr(C), ldc, M, N, K, ptr(bias), act,
-                     ptr(dref), ldr, dact, ptr(rowscale), ldrs, rs_div, accumulate, ptr(ws),
-                     ws.numel() * 4 if ws is not None else 0, splits, _stream()), "cham_gemm_f32")
-        if prof is not None:
-            e1.record()
-            c1 = self._tile_counts()
-            tile = next((i for i in range(13) if c1[i] != c0[i]), -1)
-            rec = dict(M=M, N=N, K=K, transA=transA, transB=transB, splits=int(c1[15]), act=act, dref=dref is not None, dact=dact,
-                       bias=bias is not None, rowscale=rowscale is not None, bf16=bf16, tile=tile, epi=int(c1[14]), ev=(e0, e1))
-            if x3:
-                x1 = self._tile_counts_x3()
-                xt = next((i for i in (0, 1, 2, 4, 5) if x1[i] != x0[i]), -1)
-                if xt >= 0:          # ran on a bf16x3 instance (otherwise: delegated to the native kernels, recorded above)
-                    rec.update(x3=True, tile=xt & 3, x2h=xt >= 4, epi=int(x1[6]), splits=int(x1[7]))
-            prof.append(rec)
 
-    def _tile_counts(self):
-        import ctypes
-        out = (ctypes.c_longlong * 16)()
-        self.lib.cham_gemm_launch_counts(out, 0)
-        return list(out)
-
-    def _tile_counts_x3(self):
-        import ctypes
-        out = (ctypes.c_longlong * 8)()
-        self.lib.cham_gemm_f32x3_launch_counts(out, 0)
-        return list(out)
+        def record(c0, c1):
+            rec = _launch_record(M, N, K, transA, transB, act, dref is not None, dact, bias is not None, rowscale=rowscale is not None, bf16=bf16,
+                                 splits=int(c1[0][15]), tile=next((i for i in range(13) if c1[0][i] != c0[0][i]), -1), epi=int(c1[0][14]))
+            xt = next((i for i in (0, 1, 2, 4, 5) if c1[1][i] != c0[1][i]), -1) if x3 else -1
+            if xt >= 0:          # ran on a bf16x3 instance (otherwise: delegated to the native kernels, recorded above)
+                rec.update(x3=True, tile=xt & 3, x2h=xt >= 4, epi=int(c1[1][6]), splits=int(c1[1][7]))
+            return rec
+        with self._timed(splits, ('cham_gemm_launch_counts', 'cham_gemm_f32x3_launch_counts') if x3 else ('cham_gemm_launch_counts',), record) as (ws, ws_bytes):
+            if h2scales is not None and x3 and not bf16 and self.s1_h2:
+                if dref is not None or transB:
+                    raise ValueError("the two-plane form takes the NN and TN shapes only")
+                check(self.lib.cham_gemm_f32x2h(ptr(A), lda, transA, ptr(B), ldb, transB, ptr(C), ldc, M, N, K, ptr(bias), act, ptr(rowscale), ldrs,
+                                                rs_div, accumulate, ws, ws_bytes, splits, ptr(h2scales[0]), ptr(h2scales[1]), _stream()), "cham_gemm_f32x2h")
+            else:
+                fn = self.lib.cham_gemm_bf16 if bf16 else (self.lib.cham_gemm_f32x3 if x3 else self.lib.cham_gemm_f32)
+                check(fn(ptr(A), lda, transA, ptr(B), ldb, transB, ptr(C), ldc, M, N, K, ptr(bias), act,
+                         ptr(dref), ldr, dact, ptr(rowscale), ldrs, rs_div, accumulate, ws, ws_bytes, splits, _stream()), "cham_gemm_f32")
 
     def gemm_b16(self, A, lda, transA, B, ldb, transB, C, ldc, out_f32, M, N, K, bias=None, act=ACT_NONE, dref=None, ldr=0,
                  dact=ACT_NONE, accumulate=0, splits=1, dma=False):
         """bf16-resident GEMM (csrc/gemm_b16.hip): NT (transA=0, transB=1) or TN (transA=1, transB=0).  dma: the LDS-DMA core
         (cham_gemm_b16_dma; NT with bf16 output / TN with fp32 output, M and N multiples of 256 for TN)."""
-        ws = None
-        if splits != 1:
-            ws = self._lane_ws('gemm_ws')
-        prof = self.profile
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            c0 = self._tile_counts_b16()
-            e0.record()
-        if dma:
-            if prof is not None:
-                import ctypes
-                cw0 = (ctypes.c_longlong * 8)()
-                self.lib.cham_gemm_p3_launch_counts(cw0, 0)
-            check(self.lib.cham_gemm_b16_dma(ptr(A), lda, ptr(B), ldb, transA, ptr(C), ldc, M, N, K, ptr(bias), act, ptr(dref), ldr, dact,
-                                             accumulate, ptr(ws), ws.numel() * 4 if ws is not None else 0, splits, _stream()), "cham_gemm_b16_dma")
-            if prof is not None:
-                e1.record()
-                import ctypes
-                c = (ctypes.c_longlong * 8)()
-                self.lib.cham_gemm_p3_launch_counts(c, 0)
-                prof.append(dict(M=M, N=N, K=K, transA=transA, transB=transB, splits=int(c[7]), act=act, dref=dref is not None, dact=dact,
-                                 bias=bias is not None, rowscale=False, bf16=True, b1=True, b1w=bool(c[4] > cw0[4]), out_f32=int(transA), tile=0, epi=int(c[6]),
-                                 ev=(e0, e1)))
-            return
-        check(self.lib.cham_gemm_b16(ptr(A), lda, transA, ptr(B), ldb, transB, ptr(C), ldc, out_f32, M, N, K, ptr(bias), act, ptr(dref),
-                                     ldr, dact, accumulate, ptr(ws), ws.numel() * 4 if ws is not None else 0, splits, _stream()),
-              "cham_gemm_b16")
-        if prof is not None:
-            e1.record()
-            c1 = self._tile_counts_b16()
-            tile = next((i for i in range(5) if c1[i] != c0[i]), -1)
-            prof.append(dict(M=M, N=N, K=K, transA=transA, transB=transB, splits=int(c1[7]), act=act, dref=dref is not None, dact=dact,
-                             bias=bias is not None, rowscale=False, bf16=True, b16=True, out_f32=int(c1[5]), tile=tile, epi=int(c1[6]),
-                             ev=(e0, e1)))
+        def record(c0, c1):
+            (c0,), (c,) = c0, c1
+            how = (dict(b1=True, b1w=bool(c[4] > c0[4]), out_f32=int(transA)) if dma else
+                   dict(tile=next((i for i in range(5) if c[i] != c0[i]), -1), b16=True, out_f32=int(c[5])))
+            return _launch_record(M, N, K, transA, transB, act, dref is not None, dact, bias is not None, bf16=True, splits=int(c[7]), epi=int(c[6]), **how)
+        with self._timed(splits, ('cham_gemm_p3_launch_counts' if dma else 'cham_gemm_b16_launch_counts',), record) as (ws, ws_bytes):
+            if dma:
+                check(self.lib.cham_gemm_b16_dma(ptr(A), lda, ptr(B), ldb, transA, ptr(C), ldc, M, N, K, ptr(bias), act, ptr(dref), ldr, dact,
+                                                 accumulate, ws, ws_bytes, splits, _stream()), "cham_gemm_b16_dma")
+            else:
+                check(self.lib.cham_gemm_b16(ptr(A), lda, transA, ptr(B), ldb, transB, ptr(C), ldc, out_f32, M, N, K, ptr(bias), act, ptr(dref),
+                                             ldr, dact, accumulate, ws, ws_bytes, splits, _stream()), "cham_gemm_b16")
 
     def gemm_p3(self, A, a_ps, lda, B, b_ps, ldb, tn, C, ldc, M, N, K, bias=None, act=ACT_NONE, dref_h=None, ldr=0, dact=ACT_NONE,
                 accumulate=0, splits=1):
         """Plane-product GEMM over pre-split bf16 planes (csrc/gemm_p3.hip): NT (tn=0) or TN (tn=1, split-K)."""
-        ws = None
-        if splits != 1:
-            ws = self._lane_ws('gemm_ws')
-        prof = self.profile
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        check(self.lib.cham_gemm_p3(ptr(A), a_ps, lda, ptr(B), b_ps, ldb, tn, ptr(C), ldc, M, N, K, ptr(bias), act, ptr(dref_h), ldr, dact,
-                                    accumulate, ptr(ws), ws.numel() * 4 if ws is not None else 0, splits, _stream()), "cham_gemm_p3")
-        if prof is not None:
-            e1.record()
-            import ctypes
-            c = (ctypes.c_longlong * 8)()
-            self.lib.cham_gemm_p3_launch_counts(c, 0)
-            prof.append(dict(M=M, N=N, K=K, transA=tn, transB=0 if tn else 1, splits=int(c[7]), act=act, dref=dref_h is not None, dact=dact,
-                             bias=bias is not None, rowscale=False, bf16=False, p3=True, tile=0, epi=int(c[6]), ev=(e0, e1)))
+        record = lambda c0, c1: _launch_record(M, N, K, tn, 0 if tn else 1, act, dref_h is not None, dact, bias is not None, splits=int(c1[0][7]),
+                                               epi=int(c1[0][6]), p3=True)
+        with self._timed(splits, ('cham_gemm_p3_launch_counts',), record) as (ws, ws_bytes):
+            check(self.lib.cham_gemm_p3(ptr(A), a_ps, lda, ptr(B), b_ps, ldb, tn, ptr(C), ldc, M, N, K, ptr(bias), act, ptr(dref_h), ldr, dact,
+                                        accumulate, ws, ws_bytes, splits, _stream()), "cham_gemm_p3")
 
     def gemm_h2(self, A, a_ps, lda, a_sc, B, b_ps, ldb, b_sc, tn, C, ldc, M, N, K, bias=None, act=ACT_NONE, dref_h=None, ldr=0, dact=ACT_NONE,
                 accumulate=0, splits=1, a_tiles=0, b_tiles=0, dref_blocked=0, group_rows=0, groupsum=None):
         """Plane-product GEMM over two fp16 planes + scale records (csrc/gemm_h2.hip): NT (tn=0) or TN (tn=1, split-K).  a_tiles / b_tiles > 0:
         that operand is TILE-BLOCKED with this many row tiles per plane (include/chameleon_nar.h cham_gemm_h2b), dref_blocked: dref_h likewise.
         groupsum (dgrad only): the epilogue also leaves the column sums of every group of `group_rows` rows (cham_gemm_h2_dgrad_gs)."""
-        ws = None
-        if splits != 1:
-            ws = self._lane_ws('gemm_ws')
-        prof = self.profile
-        if prof is not None:
-            import ctypes
-            c0 = (ctypes.c_longlong * 8)()
-            self.lib.cham_gemm_h2_launch_counts(c0, 0)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if groupsum is not None:
-            check(self.lib.cham_gemm_h2_dgrad_gs(ptr(A), a_ps, lda, ptr(a_sc), ptr(B), b_ps, ldb, ptr(b_sc), ptr(C), ldc, M, N, K, ptr(dref_h), ldr,
-                                                 a_tiles, dref_blocked, group_rows, ptr(groupsum), groupsum.numel() * 4, _stream()), "cham_gemm_h2_dgrad_gs")
-        else:
-            check(self.lib.cham_gemm_h2b(ptr(A), a_ps, lda, ptr(a_sc), ptr(B), b_ps, ldb, ptr(b_sc), tn, ptr(C), ldc, M, N, K, ptr(bias), act, ptr(dref_h),
-                                         ldr, dact, accumulate, ptr(ws), ws.numel() * 4 if ws is not None else 0, splits, a_tiles, b_tiles, dref_blocked,
-                                         _stream()), "cham_gemm_h2b")
-        if prof is not None:
-            e1.record()
-            c = (ctypes.c_longlong * 8)()
-            self.lib.cham_gemm_h2_launch_counts(c, 0)
-            prof.append(dict(M=M, N=N, K=K, transA=tn, transB=0 if tn else 1, splits=int(c[7]), act=act, dref=dref_h is not None, dact=dact,
-                             bias=bias is not None, rowscale=False, bf16=False, h2=True, h2w=bool(c[2] > c0[2]), h2blk=bool(c[3] > c0[3]), tile=0, epi=int(c[6]), ev=(e0, e1)))
-
-    def _tile_counts_b16(self):
-        import ctypes
-        out = (ctypes.c_longlong * 8)()
-        self.lib.cham_gemm_b16_launch_counts(out, 0)
-        return list(out)
+        def record(c0, c1):
+            (c0,), (c,) = c0, c1
+            return _launch_record(M, N, K, tn, 0 if tn else 1, act, dref_h is not None, dact, bias is not None, splits=int(c[7]), epi=int(c[6]),
+                                  h2=True, h2w=bool(c[2] > c0[2]), h2blk=bool(c[3] > c0[3]))
+        with self._timed(splits, ('cham_gemm_h2_launch_counts',), record) as (ws, ws_bytes):
+            if groupsum is not None:
+                check(self.lib.cham_gemm_h2_dgrad_gs(ptr(A), a_ps, lda, ptr(a_sc), ptr(B), b_ps, ldb, ptr(b_sc), ptr(C), ldc, M, N, K, ptr(dref_h), ldr,
+                                                     a_tiles, dref_blocked, group_rows, ptr(groupsum), groupsum.numel() * 4, _stream()), "cham_gemm_h2_dgrad_gs")
+            else:
+                check(self.lib.cham_gemm_h2b(ptr(A), a_ps, lda, ptr(a_sc), ptr(B), b_ps, ldb, ptr(b_sc), tn, ptr(C), ldc, M, N, K, ptr(bias), act, ptr(dref_h),
+                                             ldr, dact, accumulate, ws, ws_bytes, splits, a_tiles, b_tiles, dref_blocked, _stream()), "cham_gemm_h2b")
 
     def colsum(self, X, ld, R, F, out, w=None, accumulate=0, b16=False):
         ws = self._lane_ws('colsum_ws')
@@ -639,7 +536,6 @@ class NARRuntime:
 
     def side(self):
         """Context manager: run the enclosed launches on the side stream (or inline when overlap is disabled)."""
-        import contextlib
         return torch.cuda.stream(self.side_stream) if self.overlap else contextlib.nullcontext()
 
     def fork(self):
@@ -651,36 +547,42 @@ class NARRuntime:
             torch.cuda.current_stream().wait_stream(self.side_stream)
 
 
-def _h2b_block():
-    from .. import _lib
-    return int(_lib.load().cham_h2b_block_elements())
+def _launch_record(M, N, K, transA, transB, act, dref, dact, bias, rowscale=False, bf16=False, splits=1, tile=0, epi=0, **flags):
+    # one entry of rt.profile (bench.py kernel_symbol / roofline leg, scripts/gemm_breakdown.py, scripts/insitu_gemm.py)
+    return dict(M=M, N=N, K=K, transA=transA, transB=transB, splits=splits, act=act, dref=dref, dact=dact, bias=bias, rowscale=rowscale,
+                bf16=bf16, tile=tile, epi=epi, **flags)
 
 
-def blocked_plane_elements(tiles, C):
-    """Elements of ONE tile-blocked plane of `tiles` row tiles and leading dimension C (csrc/common.h h2b_index)."""
-    return tiles * (C // 32) * _h2b_block()
+def _launch_counts(fn, n=16):      # what a launch-counter entry point of the library has counted (8 or 16 counters)
+    out = (ctypes.c_longlong * n)()
+    fn(out, 0)
+    return list(out)
 
 
-def planes_from_blocked(t, tiles, C=None):
-    """[planes, >= tiles * (C / 32) * block] memory in the TILE-BLOCKED layout ([row tile][C / 32][256][32] (+ padding), csrc/common.h
-    h2b_index) -> the row-major [planes, tiles * 256, C] matrix (a copy; tests and debugging)."""
-    npl = t.shape[0]
-    C = t.shape[2] if C is None else C
-    blk = _h2b_block()
-    flat = t.reshape(npl, -1)[:, :tiles * (C // 32) * blk]
-    return flat.reshape(npl, tiles, C // 32, blk)[..., :8192].reshape(npl, tiles, C // 32, 256, 32).permute(0, 1, 3, 2, 4).reshape(npl, tiles * 256, C)
+class _TimedLaunch:
+    """NARRuntime._timed(splits, counters, record): context manager around ONE launch of the GEMM family."""
+    # Yields (pointer, bytes) of the lane's split-K workspace ((None, 0) for splits == 1); while rt.profile is a list, two HIP events on the current
+    # stream immediately around the launch and record(c0, c1) + ev=(start, end) appended for bench.py's roofline (c0 / c1: the launch counters named
+    # in `counters` before / after).  (A class, not a generator: with rt.profile None a launch pays two near-empty calls.)
+    __slots__ = ('rt', 'ws', 'counters', 'record', 'e0', 'c0')
 
+    def __init__(self, rt, splits, counters, record):
+        self.rt, self.counters, self.record = rt, counters, record
+        ws = rt._lane_ws('gemm_ws') if splits != 1 else None
+        self.ws = (ptr(ws), ws.numel() * 4) if ws is not None else (None, 0)
 
-def planes_to_blocked(t):
-    """Row-major [planes, R, C] (C % 32 == 0) -> (tile-blocked [planes, tiles * (C / 32) * block] with the rows beyond R zero, tiles)."""
-    npl, R, C = t.shape
-    tiles = -(-R // 256)
-    blk = _h2b_block()
-    pad = torch.zeros(npl, tiles * 256, C, dtype=t.dtype, device=t.device)
-    pad[:, :R] = t
-    out = torch.zeros(npl, tiles, C // 32, blk, dtype=t.dtype, device=t.device)
-    out[..., :8192] = pad.reshape(npl, tiles, 256, C // 32, 32).permute(0, 1, 3, 2, 4).reshape(npl, tiles, C // 32, 8192)
-    return out.reshape(npl, -1), tiles
+    def __enter__(self):
+        if self.rt.profile is not None:
+            self.e0, self.c0 = torch.cuda.Event(enable_timing=True), [_launch_counts(getattr(self.rt.lib, name)) for name in self.counters]
+            self.e0.record()       # torch's current stream == the stream the kernel is launched on (_stream())
+        return self.ws
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.rt.profile is not None and exc_type is None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            c1 = [_launch_counts(getattr(self.rt.lib, name)) for name in self.counters]
+            self.rt.profile.append(dict(self.record(self.c0, c1), ev=(self.e0, e1)))
 
 
 class StepPlan:
@@ -694,9 +596,7 @@ class StepPlan:
         rows = B * T * (N + 2)
         need = 4 * (4 * rows * L.C + 2 * rows * (128 + 64 + 32))        # (the bf16 configuration needs ~5/8 of this)
         if rt is not None and rt.p3:
-            rc = B * T * (N + 1)
-            need += 2 * (2 if rt.h2 else 3) * 2 * rc * L.C + 4 * B * T * L.C
-            need += 4 * int(rt.lib.cham_group_rows_segments_len(2 * B * T + 20 * N + 1))
+            need += (H2Rows if rt.h2 else P3Rows).estimate_bytes(rt, L, B, T, N)
         return need
 
     def allocated_bytes(self):
@@ -762,52 +662,12 @@ class StepPlan:
         # CAR
         self.U, self.dU = f32(BT, C), f32(BT, C)
         self.V, self.dV = f32(RV, C), f32(RV, C)
-        b16 = rt.b16
-        bf = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
-        cand = bf if b16 else f32                 # storage of the matrices with one row per candidate
-        if b16:       # clicked-input rows stay fp32 (they feed / come from the fp32 recurrent branch); candidate rows are bf16
-            self.Z1, self.Z2, self.dZ2, self.dZ1 = f32(BT, C), f32(BT, C), f32(BT, C), f32(BT, C)
-            self.Z1c, self.Z2c, self.dZ2c, self.dZ1c, self.Mc = bf(Rc, C), bf(Rc, C), bf(Rc, C), bf(Rc, C), bf(Rc, C)
-            self.b2part = f32(BT, C)
-        else:         # one [BT + Rc, C] matrix each: clicked-input rows first (Z1c ... are views taken per step: BT = valid positions)
-            # With the plane-resident CAR GEMMs the candidate rows of Z1 exist as planes only, and with the fused scorer dgrad those of
-            # dZ2 too: the fp32 matrices keep the clicked-input rows (ensure_rows() grows them on the paths that do need all rows -
-            # dropout, NC outside the fused kernel's range)
-            fused = rt.p3 and rt.dm_fused and 32 <= NC <= 256
-            self.Z1 = f32(BT if rt.p3 else Rall, C)
-            self.Z2 = f32(Rall, C)
-            self.dZ2 = f32(BT if fused else Rall, C)
-            self.dZ1 = f32(Rall, C)
-        self.p3 = rt.p3
-        self.h2 = rt.h2
-        if rt.p3:     # plane-resident operands of the three candidate-row CAR GEMMs (planes Rc * C elements apart) + b2 partial sums
-            self.z1_tiles = self.dz2_tiles = 0
-            if rt.h2:      # two fp16 planes + the scale records of the two matrices
-                # TILE-BLOCKED planes (round 6; csrc/common.h h2b_index): [row tiles of 256][C / 32][256][32] - what the NT GEMMs fetch per
-                # request is whole 128-byte lines.  Z1's planes always (cham_combine_fwd_h2b writes them); dZ2's when the fused scorer dgrad
-                # is their producer (cham_dm_mulpred_h2_blk; the unfused cham_mulpred_bwd_h2 writes row-major).  Row tiles are allocated
-                # whole (+ one: a workgroup of the fused dgrad addresses two tiles from its first row's), zero-initialised.
-                tiles = -(-Rc // 256) + 1
-                if rt.h2_blocked:
-                    self.z1_tiles = tiles if rt.h2_blocked_which in ("1", "z1") else 0
-                    self.dz2_tiles = tiles if (rt.dm_fused and 32 <= NC <= 256 and rt.h2_blocked_which in ("1", "dz2")) else 0
-                self.Z1p = (torch.zeros(2, blocked_plane_elements(self.z1_tiles, C), dtype=torch.float16, device=dev) if self.z1_tiles
-                            else torch.zeros(2, Rc, C, dtype=torch.float16, device=dev))
-                self.dZ2p = (torch.zeros(2, blocked_plane_elements(self.dz2_tiles, C), dtype=torch.float16, device=dev) if self.dz2_tiles
-                             else torch.zeros(2, Rc, C, dtype=torch.float16, device=dev))
-                self.sc_z1 = torch.zeros(8, dtype=torch.float32, device=dev)
-                self.sc_dz2 = torch.zeros(8, dtype=torch.float32, device=dev)
-                self.sc_ds1 = torch.zeros(8, dtype=torch.float32, device=dev)          # dS1 itself (operand of the Ws1 weight gradient)
-                # per-click column sums of dZ1 from the CAR dgrad's epilogue (round 6; csrc/gemm_h2.hip H2Params::gsum): dU without a second
-                # pass over the 1 GB of candidate rows
-                self.gsum = (torch.empty(int(rt.lib.cham_gemm_h2_groupsum_bytes(Rc, C, NC)) // 4, dtype=torch.float32, device=dev)
-                             if rt.dgrad_groupsum and NC >= 32 and Rc > 0 else None)
-            else:
-                self.Z1p, self.dZ2p = bf(3, Rc, C), bf(3, Rc, C)
-            self.p3_ps = Rc * C                                   # plane stride of a row-major operand ...
-            self.z1_ps = self.Z1p[0].numel()                      # ... and of each operand as allocated
-            self.dz2_ps = self.dZ2p[0].numel()
-            self.b2part = f32(BT, C)
+        # Z1, Z2, dZ2, dZ1 (+ planes, scale records, b2 partial sums) in the arithmetic the plan is built for; self.arm: the arm of the LAST
+        # step on this plan (forward() sets it, backward() and cand_Z1() read it)
+        self.gsum = self.arm = None
+        arm = rt.step_arm()
+        arm.alloc(self, f32)
+        cand = lambda *s: torch.empty(*s, dtype=torch.bfloat16 if arm.b16 else torch.float32, device=dev)      # storage of the matrices with one row per candidate
         # RNN
         self.seq_len = torch.zeros(B, dtype=torch.int32, device=dev)
         NG = L.NG
@@ -842,7 +702,11 @@ class StepPlan:
         self.neg_ids_c = i64(BT, N)
         self.neg_slot_c = torch.zeros(BT, N, dtype=torch.int32, device=dev)
         self.Z2f, self.rnn_c, self.drnn_c, self.dxproj_c = f32(BT, C), f32(BT, Hp), f32(BT, Hp), f32(BT, NG * Hp)
-        self.pos, self.P = None, BT
+        self.pos, self.P, self.PC = None, BT, Rc         # of the current step: compaction map, valid positions, candidate rows (P * NC)
+        # made on first need: the event of the side lane's row grouping (training-mode forward), the item rows a data-parallel step can touch
+        # (sparse modes), dropout_buffers(); nbytes: set by NARRuntime.plan once the plan is built
+        self.grouped_ev = self.touched = self.Xd = None
+        self.nbytes = 0
         # The zero fills above run on the stream that built the plan.  A stream that touches these buffers without being ordered behind
         # that point must wait for this event first: presample() may be the FIRST user of a plan (a padded length T seen for the first
         # time), it writes the sampler outputs on the state's stream - and the fills, still queued behind the running step, would wipe them.
@@ -856,15 +720,14 @@ class StepPlan:
         if t.shape[0] < self.Rall:
             t = torch.empty(self.Rall, t.shape[1], dtype=t.dtype, device=t.device)
             setattr(self, name, t)
-            if hasattr(self, 'nbytes'):         # what the plan cache's byte budget counts (NARRuntime.plan)
-                self.nbytes = self.allocated_bytes()
+            self.nbytes = self.allocated_bytes()         # what the plan cache's byte budget counts (NARRuntime.plan)
         return t
 
     def dropout_buffers(self, rt):
         """Buffers of the dropout path (keep_prob < 1: dense PreCAR input rows, dropped FC1 / recurrent outputs) - allocated on first use."""
         if not rt.b16:
             self.ensure_rows('Z1'); self.ensure_rows('dZ2')
-        if getattr(self, 'Xd', None) is None:
+        if self.Xd is None:
             L, dev = rt.layout, rt.device
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
             Fw = L.Fc + L.Fi
@@ -881,17 +744,7 @@ class StepPlan:
         """Candidate rows of the PreCAR output of the last step as fp32 [P * NC, C] (tests): the fp32 matrix, or the sum of its planes."""
         P = self.P if P is None else P
         n = P * self.NC
-        if getattr(self, 'used_p3', False):
-            if getattr(self, 'z1_tiles', 0):       # tile-blocked planes -> row-major
-                z = planes_from_blocked(self.Z1p, self.z1_tiles, self.C)[:, :n].float()
-            else:
-                z = self.Z1p[:, :n].float()
-            if self.h2:
-                return (z[0] + z[1]) * self.sc_z1[1]
-            return z[0] + z[1] + z[2]
-        if self.Z1.shape[0] == self.BT and hasattr(self, 'Z1c'):
-            return self.Z1c[:n].float()
-        return self.Z1[P:P + n]
+        return self.arm.cand_Z1(self, P, n)
 
     def use_sampler_set(self, k):
         self._samp_cur = k
@@ -1169,7 +1022,6 @@ class NARModuleModel:
         B, T, N = d['B'], d['T'], self.negative_samples
         pl = rt.plan(B, T, N, self.negative_sample_from_buffer, d['Bg'])
         self._plan, self._d = pl, d
-        pl.used_p3 = False
         check(lib.cham_set_log_bases(self.elapsed_days_smooth_log_base, self.popularity_smooth_log_base), "cham_set_log_bases")
         if d.get('uploaded') is not None:
             torch.cuda.current_stream().wait_event(d['uploaded'])
@@ -1186,8 +1038,8 @@ class NARModuleModel:
                 shadows_ev.record()
         # BT = rows of the row-wise stages = the P valid positions (all B*T when nothing is padded); BTf = the [B, T] layout
         pos, BT, BTf, NC, pmax = d['pos'], d['P'], pl.BT, pl.NC, pl.pmax
-        pl.pos, pl.P = pos, BT
-        Rc = BT * NC; Rall = BT + Rc; RV = 2 * BT + pmax + 1
+        Rc = BT * NC; RV = 2 * BT + pmax + 1
+        pl.pos, pl.P, pl.PC = pos, BT, Rc
         C, Hp, Fc, Fi = L.C, L.Hp, L.Fc, L.Fi
         cell, NGH = (1 if L.cell == 'gru' else 0), L.NG * L.Hp
         if step is None:
@@ -1209,7 +1061,7 @@ class NARModuleModel:
             # item rows this step can touch on ANY rank (parallel.py, mode "sparse"): GLOBAL clicked ids + candidate pool + pad item,
             # as int32 row indices in a buffer of the plan (nothing is allocated or freed around the collective)
             n1 = d['aci'].numel()
-            if getattr(pl, 'touched', None) is None or pl.touched.numel() < n1 + pmax + 1:
+            if pl.touched is None or pl.touched.numel() < n1 + pmax + 1:
                 pl.touched = torch.zeros(n1 + pmax + 1, dtype=torch.int32, device=rt.device)
             pl.touched[:n1].copy_(d['aci'].reshape(-1))
             pl.touched[n1:n1 + pmax].copy_(pl.pool)
@@ -1223,7 +1075,7 @@ class NARModuleModel:
         pl.cur_neg_ids, pl.cur_neg_slot = neg_ids, neg_slot
         # a training-mode forward on this plan that was NOT followed by backward() (a loss-only call, an exception in between) leaves the
         # side lane's row grouping un-awaited: it reads ids_all and writes perm / seg - wait for it before rewriting ids_all
-        if getattr(pl, 'grouped_ev', None) is not None:
+        if pl.grouped_ev is not None:
             torch.cuda.current_stream().wait_event(pl.grouped_ev)
         # K1 item row set = [clicked ; positives ; pool slots ; pad item 0]
         _roctx.pop(); _roctx.push("K1 features (gather, normalise, scale / center)")
@@ -1361,51 +1213,17 @@ class NARModuleModel:
                 fc1 = pl.FC1d
             rt.gemm(fc1, p('Wf2'), pl.pred, BT, C, 512, 512, C, C, bias=p('bf2'), act=ACT_TANH)
         # ... the candidate rows: PreCAR combine (HBM-bound) + the dominant GEMM, CAR layer 2 on the B*T*(1+N) rows
-        if rt.b16:
-            # bf16 configuration: candidate-row matrices are bf16 in HBM, weights through their bf16 shadows (csrc/gemm_b16.hip)
-            sh = rt.shadow
-            if drop:      # dense PreCAR rows (masks differ per occurrence): bf16-rounded operands, fp32 out, stored as the bf16-resident Z1c
-                rt.gemm(pl.Xd[BT:], self._drop['W1'], pl.Z1f[BT:], Rc, C, Fc + Fi, Fc + Fi, C, C, bias=p('b1'), act=ACT_LEAKY)
-                check(lib.cham_cast_b16(pl.Z1f[BT:].data_ptr(), Rc, C, ptr(pl.Z1c), None, s), "cham_cast_b16")
-            else:
-                check(lib.cham_combine_fwd_b16(ptr(pl.U), ptr(pl.V), C, BT, N, pmax, ptr(neg_slot), ptr(pl.Z1c), s), "cham_combine_fwd_b16")
-            rt.gemm_b16(pl.Z1c, C, 0, sh['W2T'], C, 1, pl.Z2c, C, 0, Rc, C, C, bias=p('b2'), act=ACT_TANH, dma=rt.b16_dma)
-            rt.join()
-            check(lib.cham_mul_rows_b16(ptr(pl.Z2c), ptr(pl.pred), C, BT, NC, ptr(pl.Mc), s), "cham_mul_rows_b16")
-            rt.gemm_b16(pl.Mc, C, 0, sh['Ws1T'], C, 1, pl.S1, 128, 0, Rc, 128, C, bias=p('bs1'), act=ACT_LEAKY)
-            rt.gemm_b16(pl.S1, 128, 0, sh['Ws2T'], 128, 1, pl.S2, 64, 0, Rc, 64, 128, bias=p('bs2'), act=ACT_LEAKY)
-            rt.gemm_b16(pl.S2, 64, 0, sh['Ws3T'], 64, 1, pl.S3, 32, 0, Rc, 32, 64, bias=p('bs3'), act=ACT_LEAKY)
-            softmax_fwd = lib.cham_score_softmax_fwd_b16
-        else:
-            use_p3 = pl.used_p3 = rt.p3 and not drop and Rc > 0
-            if drop:
-                rt.gemm(pl.Xd[BT:], self._drop['W1'], pl.Z1[BT:], Rc, C, Fc + Fi, Fc + Fi, C, C, bias=p('b1'), act=ACT_LEAKY)
-            elif use_p3 and rt.h2:      # candidate rows straight into two fp16 planes x 2^k, k from the bound max|U| + max|V| (no fp32 copy)
-                check(lib.cham_h2_scale_absmax(ptr(pl.U), BT * C, ptr(pl.V), RV * C, ptr(pl.sc_z1), s), "cham_h2_scale_absmax")
-                check(lib.cham_combine_fwd_h2b(ptr(pl.U), ptr(pl.V), C, BT, N, pmax, ptr(neg_slot), ptr(pl.Z1p), pl.z1_ps, ptr(pl.sc_z1), 1 if pl.z1_tiles else 0, s),
-                      "cham_combine_fwd_h2")
-            elif use_p3:      # candidate rows straight into three bf16 planes (no fp32 copy)
-                check(lib.cham_combine_fwd_p3(ptr(pl.U), ptr(pl.V), C, BT, N, pmax, ptr(neg_slot), ptr(pl.Z1p), pl.p3_ps, s), "cham_combine_fwd_p3")
-            else:
-                check(lib.cham_combine_fwd(ptr(pl.U), ptr(pl.V), C, BT, N, pmax, ptr(neg_slot), ptr(pl.Z1), BT, Rc, s), "cham_combine_fwd")
-            if use_p3 and rt.h2:
-                rt.gemm_h2(pl.Z1p, pl.z1_ps, C, pl.sc_z1, rt.w2tp, C * C, C, rt.sc_w2, 0, pl.Z2[BT:], C, Rc, C, C, bias=p('b2'), act=ACT_TANH, a_tiles=pl.z1_tiles)
-            elif use_p3:
-                rt.gemm_p3(pl.Z1p, pl.p3_ps, C, rt.w2tp, C * C, C, 0, pl.Z2[BT:], C, Rc, C, C, bias=p('b2'), act=ACT_TANH)
-            else:
-                rt.gemm(pl.Z1[BT:], p('W2'), pl.Z2[BT:], Rc, C, C, C, C, C, bias=p('b2'), act=ACT_TANH)
-            rt.join()
-            # scorer: (cand (.) pred) -> 128 -> 64 -> 32 -> 1, softmax(/tau), masked NLL
-            _roctx.pop(); _roctx.push("K5 scorer, softmax, loss")
-            Z2c = pl.Z2[BT:Rall]
-            rt.gemm(Z2c, p('Ws1'), pl.S1, Rc, 128, C, C, 128, 128, bias=p('bs1'), act=ACT_LEAKY, rowscale=pl.pred, ldrs=C, rs_div=NC,
-                    h2scales=(rt.sc_unit, rt.sc_ws1n) if rt.s1_h2_fwd else None)
-            rt.gemm(pl.S1, p('Ws2'), pl.S2, Rc, 64, 128, 128, 64, 64, bias=p('bs2'), act=ACT_LEAKY)
-            rt.gemm(pl.S2, p('Ws3'), pl.S3, Rc, 32, 64, 64, 32, 32, bias=p('bs3'), act=ACT_LEAKY)
-            softmax_fwd = lib.cham_score_softmax_fwd
-        check(softmax_fwd(ptr(pl.S3), 32, ptr(p('Ws4')), ptr(p('bs4')), BT, N, float(self.softmax_temperature),
-                          ptr(pl.mask), ptr(pl.logits), ptr(pl.probs), ptr(pl.nll), self.novelty_reg_factor,
-                          ptr(neg_ids), ptr(st['pop_norm']), ptr(pl.nov_aux), s), "cham_score_softmax_fwd")
+        # in the arithmetic of this step (nar/candidate_rows.py), decided here, once: the configured arm, the fp32 rows where planes cannot be used
+        arm = pl.arm = rt.step_arm(planes=not drop and Rc > 0)
+        arm.z1(pl, s, self._drop)
+        arm.car_fwd(pl)
+        rt.join()
+        # scorer: (cand (.) pred) -> 128 -> 64 -> 32 -> 1, softmax(/tau), masked NLL
+        _roctx.pop(); _roctx.push("K5 scorer, softmax, loss")
+        arm.scorer_fwd(pl, s)
+        check(getattr(lib, arm.softmax_fwd)(ptr(pl.S3), 32, ptr(p('Ws4')), ptr(p('bs4')), BT, N, float(self.softmax_temperature),
+                                            ptr(pl.mask), ptr(pl.logits), ptr(pl.probs), ptr(pl.nll), self.novelty_reg_factor,
+                                            ptr(neg_ids), ptr(st['pop_norm']), ptr(pl.nov_aux), s), "cham_score_softmax_fwd")
         def loss_kernels(s):
             check(lib.cham_sumsq_partial(ptr(rt.flat), L.n_reg, ptr(rt.sumsq), s), "cham_sumsq_partial")
             if dsc:
@@ -1450,19 +1268,16 @@ class NARModuleModel:
         cell, NGH = (1 if L.cell == 'gru' else 0), L.NG * L.Hp
         p, g = rt.p, rt.g
         main_stream, on = torch.cuda.current_stream(), rt.overlap
-        b16 = rt.b16
-        sh = rt.shadow
         drop = self._drop
         dropout = drop['fn'] if drop else None
-        use_p3 = getattr(pl, 'used_p3', False)
+        arm = pl.arm                     # the arithmetic of the candidate rows, as forward() chose it (nar/candidate_rows.py)
+        b16 = arm.b16
 
         def mark():                      # event on the current stream
             if not on:
                 return None
             ev = torch.cuda.Event(); ev.record()
             return ev
-
-        import contextlib
 
         @contextlib.contextmanager
         def side(*events):               # run the block on the side lane after `events`
@@ -1493,60 +1308,23 @@ class NARModuleModel:
         else:
             rt.grads[:L.emb_end].zero_()
             e_start = mark()
-        if rt.dev_scalars:      # sum(mask) from the step-scalar record (written by this step's forward)
-            check((lib.cham_score_softmax_bwd_b16_dev if b16 else lib.cham_score_softmax_bwd_dev)(
-                ptr(pl.S3), 32, ptr(p('Ws4')), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature), ptr(rt.scalars),
-                ptr(pl.ds), ptr(pl.dS3), self.novelty_reg_factor, ptr(neg_ids), ptr(self._dev_state['pop_norm']), ptr(pl.logits),
-                ptr(pl.nov_aux), s), "cham_score_softmax_bwd_dev")
-        else:
-            check((lib.cham_score_softmax_bwd_b16 if b16 else lib.cham_score_softmax_bwd)(
-                ptr(pl.S3), 32, ptr(p('Ws4')), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature), d['sum_mask'],
-                ptr(pl.ds), ptr(pl.dS3), self.novelty_reg_factor, ptr(neg_ids), ptr(self._dev_state['pop_norm']), ptr(pl.logits),
-                ptr(pl.nov_aux), s), "cham_score_softmax_bwd")
+        # (sum(mask): from the step-scalar record written by this step's forward, or by value)
+        check(getattr(lib, arm.softmax_bwd + ('_dev' if rt.dev_scalars else ''))(
+            ptr(pl.S3), 32, ptr(p('Ws4')), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
+            ptr(rt.scalars) if rt.dev_scalars else d['sum_mask'], ptr(pl.ds), ptr(pl.dS3), self.novelty_reg_factor, ptr(neg_ids),
+            ptr(self._dev_state['pop_norm']), ptr(pl.logits), ptr(pl.nov_aux), s), "cham_score_softmax_bwd")
         if self._dev_state.get('device'):
             self.articles_recent_pop_norm.note_consumed(d['aci'])      # last read of the state in a TRAIN step
         # scorer dgrad chain on this lane (three short GEMMs); the side lane takes the layer-1 weight gradient FIRST - 65 GFLOP of
         # matrix work that then runs beside the HBM-bound k_mulpred_bwd instead of beside the MFMA-bound CAR dgrad - and the small
         # (HBM-bound, split-K) weight / bias gradients of layers 2-4 after it
-        if b16:
-            rt.gemm_b16(pl.dS3, 32, 0, sh['Ws3'], 32, 1, pl.dS2, 64, 0, Rc, 64, 32, dref=pl.S2, ldr=64, dact=ACT_LEAKY)
-            rt.gemm_b16(pl.dS2, 64, 0, sh['Ws2'], 64, 1, pl.dS1, 128, 0, Rc, 128, 64, dref=pl.S1, ldr=128, dact=ACT_LEAKY)
-            Z2c, dZ2c = pl.Z2c[:Rc], pl.dZ2c[:Rc]
-        else:
-            rt.gemm(pl.dS3, p('Ws3'), pl.dS2, Rc, 64, 32, 32, 32, 64, transB=1, dref=pl.S2, ldr=64, dact=ACT_LEAKY)
-            rt.gemm(pl.dS2, p('Ws2'), pl.dS1, Rc, 128, 64, 64, 64, 128, transB=1, dref=pl.S1, ldr=128, dact=ACT_LEAKY)
-            if not (use_p3 and rt.dm_fused and 32 <= NC <= 256):
-                pl.ensure_rows('dZ2')          # the scorer layer-1 dgrad goes through HBM
-            Z2c, dZ2c = pl.Z2[BT:Rall], pl.dZ2[BT:Rall]
-        h2 = use_p3 and rt.h2
-        if h2:      # scale of the gradient at the CAR tanh from the Cauchy-Schwarz bound of dS1 Ws1^T: max row norm of dS1 x max row norm of Ws1
-            check(lib.cham_h2_scale_rownorm2(ptr(pl.dS1), Rc, pl.dS1.shape[1], pl.dS1.shape[1], rt.sc_ws1n.data_ptr() + 8, ptr(pl.sc_dz2),
-                                             ptr(pl.sc_ds1), s), "cham_h2_scale_rownorm2")
+        arm.scorer_dgrad(pl, s)
         e_dS1 = mark()     # (starting the side lane only after the next GEMM, to pair its MFMA work with k_mulpred_bwd's HBM work,
         #                      measured 0.26 ms slower: 17.28-17.33 vs 17.01-17.07 ms, A/B in one gpurun call)
-        # scorer layer-1 dgrad + cand (.) pred backward in one kernel (csrc/dm_fused.hip): dM never reaches HBM
-        dm_fused = use_p3 and rt.dm_fused and 32 <= NC <= 256
-        dm_fused_b16 = b16 and rt.dm_fused_b16 and 32 <= NC <= 256
-        if dm_fused_b16:
-            pass
-        elif b16:
-            rt.gemm_b16(pl.dS1, 128, 0, sh['Ws1'], 128, 1, dZ2c, C, 0, Rc, C, 128)
-        elif not dm_fused:
-            rt.gemm(pl.dS1, p('Ws1'), dZ2c, Rc, C, 128, 128, 128, C, transB=1)
-        def scorer_small_wgrads():       # layers 2-4: short split-K GEMMs + column sums, nothing but Adam (and the early DP bucket) waits for them
-            if b16:
-                rt.gemm_b16(pl.S1, 128, 1, pl.dS2, 64, 0, g('Ws2'), 64, 1, 128, 64, Rc, splits=0)
-                rt.colsum(pl.dS2, 64, Rc, 64, g('bs2'), b16=True)
-                rt.gemm_b16(pl.S2, 64, 1, pl.dS3, 32, 0, g('Ws3'), 32, 1, 64, 32, Rc, splits=0)
-                rt.colsum(pl.dS3, 32, Rc, 32, g('bs3'), b16=True)
-                rt.colsum(pl.S3, 32, Rc, 32, g('Ws4'), w=pl.ds, b16=True)
-            else:
-                rt.gemm(pl.S1, pl.dS2, g('Ws2'), 128, 64, Rc, 128, 64, 64, transA=1, splits=0)
-                rt.colsum(pl.dS2, 64, Rc, 64, g('bs2'))
-                rt.gemm(pl.S2, pl.dS3, g('Ws3'), 64, 32, Rc, 64, 32, 32, transA=1, splits=0)
-                rt.colsum(pl.dS3, 32, Rc, 32, g('bs3'))
-                rt.colsum(pl.S3, 32, Rc, 32, g('Ws4'), w=pl.ds)
-            rt.colsum(pl.ds, 1, Rc, 1, g('bs4'))
+        # scorer layer-1 dgrad: through HBM here, unless this step's arm takes it in one kernel with the cand (.) pred backward below
+        # (csrc/dm_fused.hip: dM never reaches HBM)
+        if not arm.fused_dz2(pl):
+            arm.s1_dgrad(pl)
         # Side lane, "critical chain first": with short sessions the CAR GEMMs shrink and the
         # main lane ends up waiting for the clicked-row gradient that comes out of the side lane's FC -> recurrent -> CAR chain (0.4 ms
         # of a 3.4 ms step in the kernel trace of the G1-like bench leg).  So that chain is enqueued ahead of every weight / bias
@@ -1554,91 +1332,25 @@ class NARModuleModel:
         # (bf16 configuration with full-length sessions: 6.26 vs 6.17 ms - the deferred gradients then land beside the W2 wgrad - so there it
         # is used for compacted, i.e. ragged, batches only: 2.23 vs 2.35 ms; fp32: 13.0 = 13.0 ms full-length, 2.95 vs 3.11 ms G1-like lengths)
         crit_first = on and (not b16 or pos is not None)
-        w2_main = bool(on and use_p3 and 0 < Rc <= rt.w2_main_rows)
+        w2_main = bool(on and arm.planes and 0 < Rc <= rt.w2_main_rows)
         # third lane for the small weight gradients (full batches of the default / six-plane fp32 arithmetic, one recurrent layer of the
         # UGRNN kind: with more layers the per-layer gradients read a buffer the next layer's backward overwrites)
-        use_aux = bool(on and rt.wgrad_aux and use_p3 and not w2_main and not b16 and L.L == 1 and cell == 0 and not L.rnn_stepwise and not drop)
-        def ws1_wgrad():
-            if b16:      # weight gradients: activations^T x gradients, both bf16 [rows, *] (TN through the LDS transpose read)
-                rt.gemm_b16(pl.Mc, C, 1, pl.dS1, 128, 0, g('Ws1'), 128, 1, C, 128, Rc, splits=0)
-                rt.colsum(pl.dS1, 128, Rc, 128, g('bs1'), b16=True)
-            else:
-                rt.gemm(Z2c, pl.dS1, g('Ws1'), C, 128, Rc, C, 128, 128, transA=1, rowscale=pl.pred, ldrs=C, rs_div=NC, splits=0,
-                        h2scales=(rt.sc_unit, pl.sc_ds1) if (rt.s1_h2 and use_p3) else None)
-                rt.colsum(pl.dS1, 128, Rc, 128, g('bs1'))
+        use_aux = bool(on and rt.wgrad_aux and arm.planes and not w2_main and L.L == 1 and cell == 0 and not L.rnn_stepwise and not drop)
         with side(e_start, e_dS1):
-            ws1_wgrad()
+            arm.s1_wgrad(pl)
             if not crit_first:
-                scorer_small_wgrads()
-        if dm_fused:
-            prof = rt.profile
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            if h2 and pl.dz2_tiles:      # ... with the planes of dZ2 written tile-blocked (ds1 / w scale records: the kernel's own products on two fp16 planes too)
-                f16 = rt.dm_f16
-                check(lib.cham_dm_mulpred_h2_blk(ptr(pl.dS1), 128, 128, ptr(rt.ws1h if f16 else rt.ws1p), C * 128, ptr(pl.sc_ds1) if f16 else None,
-                                                 ptr(rt.sc_ws1n) if f16 else None, ptr(Z2c), ptr(pl.pred), C, BT, N, ptr(pl.dZ2p), pl.dz2_ps, ptr(pl.sc_dz2),
-                                                 ptr(pl.dpred), ptr(pl.b2part), s), "cham_dm_mulpred_h2_blk")
-            elif h2:
-                if rt.dm_f16:     # the kernel's own products on two fp16 planes too
-                    check(lib.cham_dm_mulpred_h2h(ptr(pl.dS1), 128, 128, ptr(rt.ws1h), C * 128, ptr(pl.sc_ds1), ptr(rt.sc_ws1n), ptr(Z2c), ptr(pl.pred),
-                                                  C, BT, N, ptr(pl.dZ2p), pl.dz2_ps, ptr(pl.sc_dz2), ptr(pl.dpred), ptr(pl.b2part), s), "cham_dm_mulpred_h2h")
-                else:
-                    check(lib.cham_dm_mulpred_h2(ptr(pl.dS1), 128, 128, ptr(rt.ws1p), C * 128, ptr(Z2c), ptr(pl.pred), C, BT, N, ptr(pl.dZ2p), pl.dz2_ps,
-                                                 ptr(pl.sc_dz2), ptr(pl.dpred), ptr(pl.b2part), s), "cham_dm_mulpred_h2")
-            else:
-                check(lib.cham_dm_mulpred_p3(ptr(pl.dS1), 128, 128, ptr(rt.ws1p), C * 128, ptr(Z2c), ptr(pl.pred), C, BT, N, ptr(pl.dZ2p), pl.p3_ps,
-                                             ptr(pl.dpred), ptr(pl.b2part), s), "cham_dm_mulpred_p3")
-            if prof is not None:
-                e1.record()
-                prof.append(dict(M=Rc, N=C, K=128, transA=0, transB=1, splits=1, act=0, dref=False, dact=0, bias=False, rowscale=False, bf16=False,
-                                 dmf=True, h2out=bool(h2), f16p=bool(h2 and rt.dm_f16), tile=0, epi=0, ev=(e0, e1)))
-        elif dm_fused_b16:      # bf16 configuration: the same fusion over single bf16 matrices (dM rounded to bf16 where the pair stores it)
-            prof = rt.profile
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            check(lib.cham_dm_mulpred_b16(ptr(pl.dS1), 128, 128, ptr(sh['Ws1']), ptr(Z2c), ptr(pl.pred), C, BT, N, ptr(dZ2c), ptr(pl.dpred),
-                                          ptr(pl.b2part), s), "cham_dm_mulpred_b16")
-            if prof is not None:
-                e1.record()
-                prof.append(dict(M=Rc, N=C, K=128, transA=0, transB=1, splits=1, act=0, dref=False, dact=0, bias=False, rowscale=False, bf16=True,
-                                 dmf=True, tile=0, epi=0, ev=(e0, e1)))
-        elif h2:          # gradient at the CAR tanh straight into two fp16 planes + this position's share of the b2 gradient
-            check(lib.cham_mulpred_bwd_h2(ptr(dZ2c), ptr(Z2c), ptr(pl.pred), C, BT, N, ptr(pl.dpred), ptr(pl.dZ2p), pl.dz2_ps, ptr(pl.b2part),
-                                          ptr(pl.sc_dz2), s), "cham_mulpred_bwd_h2")
-        elif use_p3:      # gradient at the CAR tanh straight into three bf16 planes + this position's share of the b2 gradient
-            check(lib.cham_mulpred_bwd_p3(ptr(dZ2c), ptr(Z2c), ptr(pl.pred), C, BT, N, ptr(pl.dpred), ptr(pl.dZ2p), pl.p3_ps, ptr(pl.b2part), s),
-                  "cham_mulpred_bwd_p3")
-        else:             # k_mulpred_bwd: HBM-bound (3 GB), between two MFMA-bound GEMMs
-            check((lib.cham_mulpred_bwd_b16 if b16 else lib.cham_mulpred_bwd)(ptr(dZ2c), ptr(Z2c), ptr(pl.pred), C, BT, N, ptr(pl.dpred), s),
-                  "cham_mulpred_bwd")
+                arm.small_wgrads(pl)
+        arm.dz2(pl, s)
         e_dZ2c = mark()              # dZ2c final + dpred
         # The candidate-row dgrad of CAR layer 2 on the main lane (needs dZ2c only): the largest GEMM of the backward, ENQUEUED BEFORE the
         # side lane's long launch sequence below - in the bf16 configuration the GPU keeps up with the host, and the ~25 launches of the
         # side block (0.5-0.8 ms of host time) left this lane idle for that long (kernel-trace timeline, profiles/r02_notes.md);
         # NT layout on the 256x256 tile.
-        if b16:
-            rt.gemm_b16(dZ2c, C, 0, sh['W2'], C, 1, pl.dZ1c, C, 0, Rc, C, C, dref=pl.Z1c, ldr=C, dact=ACT_LEAKY, dma=rt.b16_dma)
-        def w2_wgrad_planes(splits):      # candidate rows' share of the W2 weight gradient from the planes (TN, split-K)
-            if h2:
-                rt.gemm_h2(pl.Z1p, pl.z1_ps, C, pl.sc_z1, pl.dZ2p, pl.dz2_ps, C, pl.sc_dz2, 1, g('W2'), C, C, C, Rc, splits=splits,
-                           a_tiles=pl.z1_tiles, b_tiles=pl.dz2_tiles)
-            else:
-                rt.gemm_p3(pl.Z1p, pl.p3_ps, C, pl.dZ2p, pl.p3_ps, C, 1, g('W2'), C, C, C, Rc, splits=splits)
-        if h2:          # planes of dZ2 x planes of W2 as stored; leaky' from the sign of Z1's h plane
-            gsum = getattr(pl, 'gsum', None) if not drop else None
-            rt.gemm_h2(pl.dZ2p, pl.dz2_ps, C, pl.sc_dz2, rt.w2p, C * C, C, rt.sc_w2, 0, pl.dZ1[BT:], C, Rc, C, C, dref_h=pl.Z1p, ldr=C, dact=ACT_LEAKY,
-                       a_tiles=pl.dz2_tiles, dref_blocked=1 if pl.z1_tiles else 0, group_rows=NC, groupsum=gsum)
-        elif use_p3:
-            rt.gemm_p3(pl.dZ2p, pl.p3_ps, C, rt.w2p, C * C, C, 0, pl.dZ1[BT:], C, Rc, C, C, dref_h=pl.Z1p, ldr=C, dact=ACT_LEAKY)
-        elif not b16 and Rc > 0:
-            rt.gemm(pl.dZ2[BT:Rall], p('W2'), pl.dZ1[BT:Rall], Rc, C, C, C, C, C, transB=1, dref=pl.Z1[BT:Rall], ldr=C, dact=ACT_LEAKY)
+        arm.car_dgrad(pl)
         e_cdgrad = mark()
         e_w2main = None
         if w2_main:      # candidate rows' share of the W2 weight gradient here, in the main lane's wait for the side lane's recurrent chain
-            w2_wgrad_planes(0)
+            arm.w2_wgrad_cand(pl, 0)
             e_w2main = mark()
         # session FCs + recurrent layers (latency-bound: one workgroup per 32 sessions) ...
         last = L.L - 1
@@ -1653,7 +1365,7 @@ class NARModuleModel:
                 rt.gemm(pl.rnn_c if pos is not None else rnn_y(last), pl.dFC1, g('Wf1'), Hp, 512, BT, Hp, 512, 512, transA=1, splits=0)
                 rt.colsum(pl.dFC1, 512, BT, 512, g('bf1'))
                 if crit_first:
-                    scorer_small_wgrads()
+                    arm.small_wgrads(pl)
                 if rt.dp_early_bucket is not None and not self._accumulating:
                     rt.dp_early_bucket(rt.grads)     # data parallel: [Wf1 .. Ws4] gradients are final - their all-reduce starts now
             rt.gemm(pl.dpred, p('Wf2'), pl.dFC1, BT, 512, C, C, C, 512, transB=1, dref=pl.FC1, ldr=512, dact=ACT_LEAKY)
@@ -1701,45 +1413,31 @@ class NARModuleModel:
                     e_dZ1in = mark()
                     if crit_first and not use_aux:
                         fc_wgrads()
-                    if b16:
-                        # ... and the CAR layer-2 weight gradient: the candidate rows (bf16, TN) + the clicked-input rows (fp32), runs beside it
-                        rt.gemm_b16(pl.Z1c, C, 1, dZ2c, C, 0, g('W2'), C, 1, C, C, Rc, splits=0, dma=rt.b16_dma)
-                        rt.gemm(pl.Z1, pl.dZ2, g('W2'), C, C, BT, C, C, C, transA=1, splits=0, accumulate=1)
-                        if dm_fused_b16:      # the per-position sums of the stored gradient rows, written by the fused kernel
-                            rt.colsum(pl.b2part, C, BT, C, g('b2'))
-                        else:
-                            rt.colsum(dZ2c, C, Rc, C, g('b2'), b16=True)
-                        rt.colsum(pl.dZ2, C, BT, C, g('b2'), accumulate=1)
-                    elif use_p3 and use_aux:
+                    if use_aux:
                         # (round 5) the small weight / bias gradients leave this lane for the third one - every producer they read is
                         # final at e_dZ1in - and the W2 weight gradient (candidate rows from the planes, TN split-K, + the clicked rows)
                         # starts the moment the main lane's CAR dgrad has finished, not behind ~1 ms of small launches
                         with aux(e_dZ1in):
                             if crit_first:
                                 fc_wgrads()
-                            rt.colsum(pl.b2part, C, BT, C, g('b2'))
-                            rt.colsum(pl.dZ2, C, BT, C, g('b2'), accumulate=1)
+                            arm.b2_grad(pl)
                             rt.gemm(pl.Z2, dxp, g('rnn0/Wx'), C, NGH, BT, C, NGH, NGH, transA=1, splits=0)
                             rt.gemm(pl.hprev[0], pl.dxproj, g('rnn0/Wh'), Hp, 2 * Hp, BTf, Hp, NGH, 2 * Hp, transA=1, splits=0, force_f32=True)
                             rt.colsum(pl.dxproj, NGH, BTf, NGH, g('rnn0/b'))
                             e_auxdone = mark()
                         rt.side_stream.wait_event(e_cdgrad)
-                        w2_wgrad_planes(rt.p3_w2_splits)
-                        rt.gemm(pl.Z1, pl.dZ2, g('W2'), C, C, BT, C, C, C, transA=1, splits=0, accumulate=1)
+                        arm.w2_wgrad(pl, rt.p3_w2_splits)
                         continue
-                    elif use_p3:
+                    elif arm.planes:
                         # ... and the CAR layer-2 weight gradient: the candidate rows from their planes (TN, split-K), the clicked-input
                         # rows (fp32) added by the on-the-fly kernel; b2 from the per-position partial sums of k_mulpred_bwd_p3
                         def w2_grads():
                             if w2_main:       # (the candidate rows' share was written by the main lane: behind e_cdgrad it is complete)
                                 rt.side_stream.wait_event(e_w2main)
-                            else:
-                                if on:
-                                    rt.side_stream.wait_event(e_cdgrad)
-                                w2_wgrad_planes(rt.p3_w2_splits)
-                            rt.gemm(pl.Z1, pl.dZ2, g('W2'), C, C, BT, C, C, C, transA=1, splits=0, accumulate=1)
-                        rt.colsum(pl.b2part, C, BT, C, g('b2'))
-                        rt.colsum(pl.dZ2, C, BT, C, g('b2'), accumulate=1)
+                            elif on:
+                                rt.side_stream.wait_event(e_cdgrad)
+                            arm.w2_wgrad(pl, rt.p3_w2_splits, cand=not w2_main)
+                        arm.b2_grad(pl)
                         if on and not w2_main:
                             # the plane weight gradient waits for the main lane's CAR dgrad (two one-workgroup-per-CU matrix kernels only
                             # time-slice the chip): everything this lane still has to do that does NOT wait - bias sums, the recurrent and
@@ -1748,11 +1446,12 @@ class NARModuleModel:
                         else:
                             w2_grads()
                     else:
-                        # ... and the CAR layer-2 weight gradient over ALL rows, the second-largest GEMM of the step, runs beside it
-                        if on:
+                        # ... and the CAR layer-2 weight gradient (fp32: over ALL rows, the second-largest GEMM of the step - behind the CAR
+                        # dgrad; bf16-resident: the candidate rows (TN) + the clicked-input rows, beside it)
+                        if on and not b16:
                             rt.side_stream.wait_event(e_cdgrad)
-                        rt.gemm(pl.Z1, pl.dZ2, g('W2'), C, C, Rall, C, C, C, transA=1, splits=0)
-                        rt.colsum(pl.dZ2, C, Rall, C, g('b2'))
+                        arm.w2_wgrad(pl)
+                        arm.b2_grad(pl)
                     rt.gemm(pl.Z2, dxp, g('rnn0/Wx'), C, NGH, BT, C, NGH, NGH, transA=1, splits=0)
                 else:
                     rt.gemm(pl.dxproj, p('rnn%d/Wx' % l), pl.drnn, BTf, Hp, NGH, NGH, NGH, Hp, transB=1)
@@ -1772,11 +1471,7 @@ class NARModuleModel:
             if drop:        # dense PreCAR backward: one weight gradient over all CAR rows, d(input rows) masked, then summed per
                 #             position / per item row by the same deterministic scatter as the factorised path (width Fc + Fi)
                 Fw = drop['Fw']
-                dZ1 = pl.dZ1
-                if b16:      # fp32 image of [clicked rows (fp32) ; candidate rows (bf16-resident)] for the dense PreCAR backward
-                    dZ1 = pl.dZ1f
-                    dZ1[:BT].copy_(pl.dZ1[:BT])
-                    check(lib.cham_upcast_b16(ptr(pl.dZ1c), Rc * C, dZ1[BT:].data_ptr(), st), "cham_upcast_b16")
+                dZ1 = arm.dense_dZ1(pl, st)
                 rt.gemm(pl.Xd, dZ1, drop['gW1'], Fw, C, Rall, Fw, C, C, transA=1, splits=0)
                 rt.colsum(dZ1, C, Rall, C, g('b1'))
                 rt.gemm(dZ1, drop['W1'], pl.dXd, Rall, Fw, C, C, C, Fw, transB=1)
@@ -1785,15 +1480,8 @@ class NARModuleModel:
                 check(lib.cham_combine_bwd(ptr(pl.dXd), Fw, BT, N, pmax, ptr(neg_slot), ptr(pl.dUx), ptr(pl.dVx), ptr(pl.drop_ws),
                                            pl.drop_ws.numel() * 4, st), "cham_combine_bwd")
                 pl.dXc[:BT].copy_(pl.dUx[:BT, :Fc]); pl.dXi[:RV].copy_(pl.dVx[:RV, Fc:])
-            elif b16:
-                check(lib.cham_combine_bwd_b16(ptr(pl.dZ1), ptr(pl.dZ1c), C, BT, N, pmax, ptr(neg_slot), ptr(pl.dU), ptr(pl.dV), ptr(ws),
-                                               ws.numel() * 4, st), "cham_combine_bwd_b16")
-            elif h2 and getattr(pl, 'gsum', None) is not None:      # dU from the group sums of the CAR dgrad's epilogue
-                check(lib.cham_combine_bwd_gs(ptr(pl.dZ1), C, BT, N, pmax, ptr(neg_slot), ptr(pl.dU), ptr(pl.dV), ptr(ws), ws.numel() * 4,
-                                              ptr(pl.gsum), pl.gsum.numel() * 4, st), "cham_combine_bwd_gs")
             else:
-                check(lib.cham_combine_bwd(ptr(pl.dZ1), C, BT, N, pmax, ptr(neg_slot), ptr(pl.dU), ptr(pl.dV), ptr(ws), ws.numel() * 4, st),
-                      "cham_combine_bwd")
+                arm.combine_bwd(pl, ws, st)
             n_rows_cat = d['cat'].shape[1]
 
             def feature_bwd(dX, Xraw, R, F, gname, bname):
@@ -1822,7 +1510,7 @@ class NARModuleModel:
                 feature_bwd(pl.dXi, pl.Xi_raw, RV, Fi, 'gamma_item', 'beta_item')
                 for kind, feat, c0, dim, card, off in rt.item_emb_groups:
                     if kind == COL_ITEMEMB:
-                        if getattr(pl, 'grouped_ev', None) is not None:
+                        if pl.grouped_ev is not None:
                             torch.cuda.current_stream().wait_event(pl.grouped_ev)
                         check(lib.cham_emb_grad_grouped(ptr(pl.dXi), RV, Fi, c0, dim, ptr(p('gamma_item')), ptr(pl.ids_all), ptr(pl.perm),
                                                         ptr(pl.seg), rt.grads.data_ptr() + 4 * off, _stream()), "cham_emb_grad_grouped")
