@@ -580,6 +580,9 @@ extern "C" int cham_rnn_bwd(int cell_kind, const float* dout, const float* WhT, 
 // the reference's hypertuning searches rnn_units up to 1024, nar_mlengine_hypertuning.yaml:28-33): the host runs the
 // recurrent products h W_h as GEMM launches per time step (csrc/gemm.hip) and these kernels do the gate arithmetic,
 // length masking and state carry.  zh = h_{t-1} W_h for the step (UGRNN: [B, 2Hp]; GRU gates: [B, 2Hp], candidate: [B, Hp]).
+// UGRNN: one GEMM + one kernel per step and direction (k_ugrnn_point_*); GRU: two of each (k_gru_point_*, further down).
+// Every saved plane is written at every t, also beyond a session's length, as the fused kernels do; one thread per (b, hidden)
+// element, plain stores, no atomics: two runs are bit-identical.
 __global__ __launch_bounds__(256) void k_ugrnn_point_fwd(const float* __restrict__ xproj, const float* __restrict__ zh,
                                                          const int* __restrict__ seq_len, int B, int T, int t, int Hp,
                                                          float* __restrict__ h /*[B,Hp] state in/out*/, float* __restrict__ out,
@@ -635,3 +638,109 @@ extern "C" int cham_ugrnn_point_bwd(const float* dout, const float* carry, const
     CHAM_CHECK_LAUNCH();
     return CHAM_OK;
 }
+
+// GRU step-wise: the candidate needs r * h of ALL hidden units, so a time step is two recurrent GEMMs with a gate kernel behind each.
+// forward:  zg [B,2Hp] = h W_gh -> gates (r, u; saves hprev, R, G = u, RH = r h) -> zc [B,Hp] = RH[:,t] W_ch -> out (c, h', out, Cc, state)
+// backward: c (dz_u, dz_c, direct = dh u) -> drh [B,Hp] = dzc W_ch^T -> r (dz_r; direct += drh r) -> carry_next = direct + dzs W_gh^T
+__global__ __launch_bounds__(256) void k_gru_point_gates_fwd(const float* __restrict__ xproj, const float* __restrict__ zg, int B, int T,
+                                                             int t, int Hp, const float* __restrict__ h, float* __restrict__ hprev,
+                                                             float* __restrict__ U, float* __restrict__ R, float* __restrict__ RH) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * Hp) return;
+    const int b = i / Hp, hid = i % Hp;
+    const size_t bt = (size_t)b * T + t, o = bt * Hp + hid;
+    const float r = sigmoidf_(zg[(size_t)b * 2 * Hp + hid] + xproj[bt * 3 * Hp + hid]);
+    const float u = sigmoidf_(zg[(size_t)b * 2 * Hp + Hp + hid] + xproj[bt * 3 * Hp + Hp + hid]);
+    const float ho = h[i];
+    hprev[o] = ho; R[o] = r; U[o] = u; RH[o] = r * ho;
+}
+__global__ __launch_bounds__(256) void k_gru_point_out_fwd(const float* __restrict__ xproj, const float* __restrict__ zc,
+                                                           const int* __restrict__ seq_len, int B, int T, int t, int Hp,
+                                                           const float* __restrict__ U, const float* __restrict__ hprev,
+                                                           float* __restrict__ h /*[B,Hp] state in/out*/, float* __restrict__ out,
+                                                           float* __restrict__ Cc) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * Hp) return;
+    const int b = i / Hp, hid = i % Hp;
+    const size_t bt = (size_t)b * T + t, o = bt * Hp + hid;
+    const float c = cham_tanhf(zc[i] + xproj[bt * 3 * Hp + 2 * Hp + hid]);
+    const float u = U[o], ho = hprev[o], hn = u * ho + (1.f - u) * c;
+    const bool valid = t < seq_len[b];
+    out[o] = valid ? hn : 0.f; Cc[o] = c;
+    if (valid) h[i] = hn;
+}
+// dh = dout[:,t] + carry;  dz_u, dz_c -> dxproj[:,t];  dzc [B,Hp] (for drh = dzc W_ch^T, a GEMM);  the u half of dzs [B,2Hp];  direct [B,Hp]
+__global__ __launch_bounds__(256) void k_gru_point_c_bwd(const float* __restrict__ dout, const float* __restrict__ carry,
+                                                         const int* __restrict__ seq_len, int B, int T, int t, int Hp,
+                                                         const float* __restrict__ hprev, const float* __restrict__ U,
+                                                         const float* __restrict__ Cc, float* __restrict__ dxproj,
+                                                         float* __restrict__ dzc_out, float* __restrict__ dzs, float* __restrict__ direct) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * Hp) return;
+    const int b = i / Hp, hid = i % Hp;
+    const size_t bt = (size_t)b * T + t, o = bt * Hp + hid;
+    float dzu = 0.f, dzc = 0.f, dd = carry[i];                 // beyond the session's length the carry passes through unchanged
+    if (t < seq_len[b]) {
+        const float dh = dout[o] + carry[i];
+        const float u = U[o], c = Cc[o], hp = hprev[o];
+        dzu = dh * (hp - c) * u * (1.f - u);
+        dzc = dh * (1.f - u) * (1.f - c * c);
+        dd = dh * u;
+    }
+    dxproj[bt * 3 * Hp + Hp + hid] = dzu; dxproj[bt * 3 * Hp + 2 * Hp + hid] = dzc;
+    dzc_out[i] = dzc; dzs[(size_t)b * 2 * Hp + Hp + hid] = dzu;
+    direct[i] = dd;
+}
+// drh = d(r h_prev);  dz_r -> dxproj[:,t] and the r half of dzs;  direct += drh r  (carry_next = direct + dzs W_gh^T, a GEMM)
+__global__ __launch_bounds__(256) void k_gru_point_r_bwd(const float* __restrict__ drh, const int* __restrict__ seq_len, int B, int T,
+                                                         int t, int Hp, const float* __restrict__ hprev, const float* __restrict__ R,
+                                                         float* __restrict__ dxproj, float* __restrict__ dzs, float* __restrict__ direct) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * Hp) return;
+    const int b = i / Hp, hid = i % Hp;
+    const size_t bt = (size_t)b * T + t, o = bt * Hp + hid;
+    float dzr = 0.f;
+    if (t < seq_len[b]) {                                      // (beyond the length dzc = 0, so drh = 0: direct stays the carry)
+        const float r = R[o], d = drh[i];
+        dzr = d * hprev[o] * r * (1.f - r);
+        direct[i] += d * r;
+    }
+    dxproj[bt * 3 * Hp + hid] = dzr;
+    dzs[(size_t)b * 2 * Hp + hid] = dzr;
+}
+#define GRU_POINT_BAD_DIMS (B <= 0 || T <= 0 || Hp <= 0 || t < 0 || t >= T)
+extern "C" int cham_gru_point_gates_fwd(const float* xproj, const float* zg, const int32_t* seq_len, int B, int T, int t, int Hp,
+                                        const float* h, float* hprev, float* G, float* R, float* RH, void* stream) {
+    if (!xproj || !zg || !seq_len || !h || !hprev || !G || !R || !RH || GRU_POINT_BAD_DIMS) return -CHAM_ERR_ARG;
+    hipLaunchKernelGGL(k_gru_point_gates_fwd, dim3((B * Hp + 255) / 256), dim3(256), 0, (hipStream_t)stream, xproj, zg, B, T, t, Hp, h,
+                       hprev, G, R, RH);
+    CHAM_CHECK_LAUNCH();
+    return CHAM_OK;
+}
+extern "C" int cham_gru_point_out_fwd(const float* xproj, const float* zc, const int32_t* seq_len, int B, int T, int t, int Hp,
+                                      const float* G, const float* hprev, float* h, float* out, float* Cc, void* stream) {
+    if (!xproj || !zc || !seq_len || !G || !hprev || !h || !out || !Cc || GRU_POINT_BAD_DIMS) return -CHAM_ERR_ARG;
+    hipLaunchKernelGGL(k_gru_point_out_fwd, dim3((B * Hp + 255) / 256), dim3(256), 0, (hipStream_t)stream, xproj, zc, seq_len, B, T, t, Hp,
+                       G, hprev, h, out, Cc);
+    CHAM_CHECK_LAUNCH();
+    return CHAM_OK;
+}
+extern "C" int cham_gru_point_c_bwd(const float* dout, const float* carry, const int32_t* seq_len, int B, int T, int t, int Hp,
+                                    const float* hprev, const float* G, const float* Cc, float* dxproj, float* dzc, float* dzs,
+                                    float* direct, void* stream) {
+    if (!dout || !carry || !seq_len || !hprev || !G || !Cc || !dxproj || !dzc || !dzs || !direct || GRU_POINT_BAD_DIMS)
+        return -CHAM_ERR_ARG;
+    hipLaunchKernelGGL(k_gru_point_c_bwd, dim3((B * Hp + 255) / 256), dim3(256), 0, (hipStream_t)stream, dout, carry, seq_len, B, T, t, Hp,
+                       hprev, G, Cc, dxproj, dzc, dzs, direct);
+    CHAM_CHECK_LAUNCH();
+    return CHAM_OK;
+}
+extern "C" int cham_gru_point_r_bwd(const float* drh, const int32_t* seq_len, int B, int T, int t, int Hp, const float* hprev,
+                                    const float* R, float* dxproj, float* dzs, float* direct, void* stream) {
+    if (!drh || !seq_len || !hprev || !R || !dxproj || !dzs || !direct || GRU_POINT_BAD_DIMS) return -CHAM_ERR_ARG;
+    hipLaunchKernelGGL(k_gru_point_r_bwd, dim3((B * Hp + 255) / 256), dim3(256), 0, (hipStream_t)stream, drh, seq_len, B, T, t, Hp, hprev,
+                       R, dxproj, dzs, direct);
+    CHAM_CHECK_LAUNCH();
+    return CHAM_OK;
+}
+#undef GRU_POINT_BAD_DIMS

@@ -52,15 +52,12 @@ class ParamLayout:
             raise ValueError("CAR_embedding_size must be a multiple of 4")
         self.H = H = rnn_units
         self.Hp = Hp = ceil_to(H, 128)
-        if Hp > 512 and rnn_cell != 'ugrnn':
-            raise ValueError("rnn_units > 384 is not supported by the GRU recurrent kernel")
-        self.rnn_stepwise = Hp > 512            # UGRNN beyond the fused kernel's LDS budget: GEMM + pointwise kernel per time step
+        # beyond the fused kernels' LDS budget (UGRNN Hp 512, GRU Hp 384): GEMM + pointwise kernel per time step (GRU: two of each)
+        self.rnn_stepwise = Hp > 512 or (rnn_cell == 'gru' and Hp > 384)
         self.L = rnn_num_layers
         self.cell = rnn_cell
         if rnn_cell not in ('ugrnn', 'gru'):
             raise ValueError("rnn_cell=%r: 'ugrnn' (the reference's cell, nar_model.py:1317) or 'gru'" % rnn_cell)
-        if rnn_cell == 'gru' and Hp > 384:
-            raise ValueError("rnn_units > 384 is not supported by the GRU recurrent kernel (LDS budget)")
         self.NG = 2 if rnn_cell == 'ugrnn' else 3          # gate/candidate column blocks of the input projection
         self.n_items = n_items
         self.D = ace_dim

@@ -685,6 +685,8 @@ class StepPlan:
         if L.rnn_stepwise:
             self.h_state, self.zh, self.carry = f32(B, Hp), f32(B, 2 * Hp), f32(B, Hp)
             self.dzs, self.direct = f32(B, 2 * Hp), f32(B, Hp)
+            if gru:      # the candidate's recurrent product and its two gradients (zh / dzs hold the r | u columns of the gate GEMM)
+                self.zc, self.dzc, self.drh = f32(B, Hp), f32(B, Hp), f32(B, Hp)
         # FCs / scorer
         self.FC1, self.dFC1 = f32(BT, 512), f32(BT, 512)
         self.pred, self.dpred = f32(BT, C), f32(BT, C)
@@ -1184,7 +1186,19 @@ class NARModuleModel:
                 x = pl.Z2f
             for l in range(L.L):
                 rt.gemm(x, p('rnn%d/Wx' % l), pl.xproj[l], BTf, NGH, K, ldx, NGH, NGH, bias=p('rnn%d/b' % l))
-                if L.rnn_stepwise:      # large hidden size: one GEMM (h W_h) + one gate kernel per time step
+                if L.rnn_stepwise and cell == 1:      # GRU: gates, then the candidate over r * h - two GEMMs + two kernels per time step
+                    pl.h_state.zero_()
+                    rh = pl.RH[l].view(B, T * Hp)
+                    for t in range(T):
+                        rt.gemm(pl.h_state, p('rnn%d/Wh' % l), pl.zh, B, 2 * Hp, Hp, Hp, 2 * Hp, 2 * Hp, force_f32=True)
+                        check(lib.cham_gru_point_gates_fwd(ptr(pl.xproj[l]), ptr(pl.zh), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.h_state),
+                                                           ptr(pl.hprev[l]), ptr(pl.G[l]), ptr(pl.R[l]), ptr(pl.RH[l]), _stream()),
+                              "cham_gru_point_gates_fwd")
+                        rt.gemm(rh[:, t * Hp:], p('rnn%d/Wch' % l), pl.zc, B, Hp, Hp, T * Hp, Hp, Hp, force_f32=True)      # RH[:, t], strided
+                        check(lib.cham_gru_point_out_fwd(ptr(pl.xproj[l]), ptr(pl.zc), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.G[l]),
+                                                         ptr(pl.hprev[l]), ptr(pl.h_state), ptr(pl.rnn_out[l]), ptr(pl.Cc[l]), _stream()),
+                              "cham_gru_point_out_fwd")
+                elif L.rnn_stepwise:    # large hidden size: one GEMM (h W_h) + one gate kernel per time step
                     pl.h_state.zero_()
                     for t in range(T):
                         rt.gemm(pl.h_state, p('rnn%d/Wh' % l), pl.zh, B, 2 * Hp, Hp, Hp, 2 * Hp, 2 * Hp, force_f32=True)
@@ -1382,7 +1396,19 @@ class NARModuleModel:
             if drop:
                 dropout(pl.drnn, pl.drnn, BTf, Hp, Hp, 20 + last, 20 + last, 1, None)
             for l in range(last, -1, -1):
-                if L.rnn_stepwise:
+                if L.rnn_stepwise and cell == 1:
+                    pl.carry.zero_()
+                    for t in range(T - 1, -1, -1):
+                        check(lib.cham_gru_point_c_bwd(ptr(pl.drnn), ptr(pl.carry), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.hprev[l]),
+                                                       ptr(pl.G[l]), ptr(pl.Cc[l]), ptr(pl.dxproj), ptr(pl.dzc), ptr(pl.dzs), ptr(pl.direct),
+                                                       ss), "cham_gru_point_c_bwd")
+                        rt.gemm(pl.dzc, p('rnn%d/Wch' % l), pl.drh, B, Hp, Hp, Hp, Hp, Hp, transB=1, force_f32=True)     # d(r h) = dzc W_ch^T
+                        check(lib.cham_gru_point_r_bwd(ptr(pl.drh), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.hprev[l]), ptr(pl.R[l]),
+                                                       ptr(pl.dxproj), ptr(pl.dzs), ptr(pl.direct), ss), "cham_gru_point_r_bwd")
+                        # carry = direct + [dz_r | dz_u] W_gh^T  (rows beyond their length: dzs = 0, direct = carry -> unchanged)
+                        pl.carry.copy_(pl.direct)
+                        rt.gemm(pl.dzs, p('rnn%d/Wh' % l), pl.carry, B, Hp, 2 * Hp, 2 * Hp, 2 * Hp, Hp, transB=1, accumulate=1, force_f32=True)
+                elif L.rnn_stepwise:
                     pl.carry.zero_()
                     for t in range(T - 1, -1, -1):
                         check(lib.cham_ugrnn_point_bwd(ptr(pl.drnn), ptr(pl.carry), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.hprev[l]),

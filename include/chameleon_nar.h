@@ -417,7 +417,7 @@ int cham_ugrnn_fwd_coop(const float* xproj, const float* Wh, const int32_t* seq_
 int cham_ugrnn_bwd_coop(const float* dout, const float* Wh, const int32_t* seq_len, int B, int T, int Hp, const float* hprev, const float* G,
                         const float* Cc, float* dxproj, void* workspace, size_t workspace_bytes, void* stream);
 int cham_rnn_coop_timeouts(const void* workspace, int B, int Hp, void* stream);
-/* step-wise fallback for rnn_units beyond the fused kernels' LDS budget (UGRNN Hp > 512; hypertuning goes to 1024,
+/* step-wise fallback for rnn_units beyond the fused kernels' LDS budget (UGRNN Hp > 512, GRU Hp > 384; hypertuning goes to 1024,
  * nar_mlengine_hypertuning.yaml:28-33): the caller computes zh = h_{t-1} W_h (forward) / carry_next = direct + dzs W_h^T
  * (backward) with cham_gemm_f32 per time step; these do the UGRNN gate arithmetic, length masking and state carry */
 int cham_ugrnn_point_fwd(const float* xproj, const float* zh, const int32_t* seq_len, int B, int T, int t, int Hp, float* h,
@@ -425,6 +425,25 @@ int cham_ugrnn_point_fwd(const float* xproj, const float* zh, const int32_t* seq
 int cham_ugrnn_point_bwd(const float* dout, const float* carry, const int32_t* seq_len, int B, int T, int t, int Hp,
                          const float* hprev, const float* G, const float* Cc, float* dxproj, float* dzs, float* direct,
                          void* stream);
+/* the same for the GRU (cell_kind 1 contracts: xproj / dxproj [B,T,3Hp] in blocks r | u | c, planes [B,T,Hp]); the candidate needs
+ * r * h_prev of all hidden units, so a time step is two recurrent GEMMs with one of these kernels behind each:
+ *   forward   zg [B,2Hp] = h W_gh;  gates_fwd: r, u = sigmoid(zg + x_ru), writes hprev[:,t] = h, R, G (= u), RH (= r h);
+ *             zc [B,Hp] = RH[:,t] W_ch (A is the strided view, lda = T Hp);  out_fwd: c = tanh(zc + x_c), h' = u h + (1-u) c,
+ *             out[:,t] = t < len ? h' : 0, Cc[:,t] = c, h = h' where t < len
+ *   backward  (t descending, carry [B,Hp] starting at 0)  c_bwd: dh = dout[:,t] + carry; the u and c blocks of dxproj[:,t], dzc [B,Hp],
+ *             the u half of dzs [B,2Hp], direct = dh u (beyond the length: zeros and direct = carry);  drh [B,Hp] = dzc W_ch^T;
+ *             r_bwd: the r block of dxproj[:,t] and the r half of dzs = drh hprev r (1-r), direct += drh r;  carry = direct + dzs W_gh^T
+ * Every plane is written at every t, also beyond a session's length; rows >= B are not touched; plain stores (two runs are
+ * bit-identical).  NULL pointers or t outside [0, T): -EINVAL, nothing launched. */
+int cham_gru_point_gates_fwd(const float* xproj, const float* zg, const int32_t* seq_len, int B, int T, int t, int Hp, const float* h,
+                             float* hprev, float* G, float* R, float* RH, void* stream);
+int cham_gru_point_out_fwd(const float* xproj, const float* zc, const int32_t* seq_len, int B, int T, int t, int Hp, const float* G,
+                           const float* hprev, float* h, float* out, float* Cc, void* stream);
+int cham_gru_point_c_bwd(const float* dout, const float* carry, const int32_t* seq_len, int B, int T, int t, int Hp,
+                         const float* hprev, const float* G, const float* Cc, float* dxproj, float* dzc, float* dzs, float* direct,
+                         void* stream);
+int cham_gru_point_r_bwd(const float* drh, const int32_t* seq_len, int B, int T, int t, int Hp, const float* hprev, const float* R,
+                         float* dxproj, float* dzs, float* direct, void* stream);
 int cham_transpose_f32(const float* in, int rows, int cols, float* out, void* stream);
 /* valid-position compaction (the mask of nar_model.py:231 applied as a row selection instead of a multiply): rows are
  * `words` 32-bit words wide; gather: dst[i] = src[pos[i]], scatter: dst[pos[i]] = src[i] (other rows of dst untouched) */

@@ -1,0 +1,166 @@
+#!/usr/bin/env python
+"""Time of the recurrent stack alone, forward + backward of one layer, as nar_model.py launches it: the step-wise GRU (rnn_units above
+384) next to the step-wise UGRNN and the fused GRU.  Full-length sessions; the x W_x projection and the weight gradients are not part of
+it (they are the same GEMMs for every path).
+
+  python scripts/bench_rnn_stepwise.py [--batch 256] [--seq 20] [--warmup 5] [--iters 20] [--rounds 3] [--out FILE]
+
+Each case is warmed up, then timed with device events around one forward + backward, `iters` times per round; the rounds go through the
+cases in turn, so that a drift of the machine touches all of them.  Reported per case: median / min / max over all timed iterations
+(ms), launches per time step, and the same median at a batch of 32 sessions: where that is about the time at the full batch, the path
+is bound by its launches and their latency, not by its arithmetic.  One JSON line per case, then a markdown table."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from chameleon_recsys_amd import _lib                     # noqa: E402
+from chameleon_recsys_amd._lib import check, ptr         # noqa: E402
+
+CASES = [('gru', 512), ('gru', 1024), ('ugrnn', 640), ('ugrnn', 1024), ('gru', 384)]
+
+
+def stepwise(cell, Hp):
+    """ParamLayout.rnn_stepwise."""
+    return Hp > 512 or (cell == 'gru' and Hp > 384)
+
+
+class Stack:
+    """Buffers of one recurrent layer and the launch sequence of nar_model.py's forward / backward for it."""
+
+    def __init__(self, lib, cell, Hp, B, T, dev, seed=0):
+        self.lib, self.cell, self.Hp, self.B, self.T = lib, cell, Hp, B, T
+        self.gru, self.step = cell == 'gru', stepwise(cell, Hp)
+        ng = 3 if self.gru else 2
+        g = torch.Generator(device=dev)
+        g.manual_seed(seed + Hp)
+        rnd = lambda *s: torch.randn(*s, generator=g, device=dev, dtype=torch.float32)
+        f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+        # W_gh [Hp, 2Hp] directly followed by W_ch [Hp, Hp], as the flat parameter buffer holds them
+        self.W = rnd(Hp * (3 if self.gru else 2) * Hp) * Hp ** -0.5
+        self.Wh, self.Wch = self.W[:2 * Hp * Hp].view(Hp, 2 * Hp), (self.W[2 * Hp * Hp:].view(Hp, Hp) if self.gru else None)
+        self.WhT = f32(ng * Hp, Hp)
+        self.xproj, self.dout = 0.7 * rnd(B * T, ng * Hp), rnd(B * T, Hp)
+        self.seq_len = torch.full((B,), T, dtype=torch.int32, device=dev)
+        self.out, self.hprev, self.G, self.Cc, self.R, self.RH = (f32(B * T, Hp) for _ in range(6))
+        self.dxproj = f32(B * T, ng * Hp)
+        self.h, self.zh, self.carry, self.dzs, self.direct = f32(B, Hp), f32(B, 2 * Hp), f32(B, Hp), f32(B, 2 * Hp), f32(B, Hp)
+        self.zc, self.dzc, self.drh = f32(B, Hp), f32(B, Hp), f32(B, Hp)
+        # launches per time step (forward, backward): GEMMs + kernels (+ the carry copy)
+        self.launches = ((4, 5) if self.gru else (2, 3)) if self.step else (0, 0)
+
+    def gemm(self, A, lda, Bm, ldb, C, ldc, M, N, K, transB=0, accumulate=0):
+        check(self.lib.cham_gemm_f32(ptr(A), lda, 0, ptr(Bm), ldb, transB, ptr(C), ldc, M, N, K, None, 0, None, 0, 0, None, 0, 1, accumulate,
+                                     None, 0, 1, torch.cuda.current_stream().cuda_stream), "cham_gemm_f32")
+
+    def forward(self):
+        lib, B, T, Hp, st = self.lib, self.B, self.T, self.Hp, torch.cuda.current_stream().cuda_stream
+        if not self.step:
+            check(lib.cham_rnn_fwd(1 if self.gru else 0, ptr(self.xproj), ptr(self.W), ptr(self.seq_len), B, T, Hp, ptr(self.out), ptr(self.hprev),
+                                   ptr(self.G), ptr(self.Cc), ptr(self.R) if self.gru else None, ptr(self.RH) if self.gru else None, st), "cham_rnn_fwd")
+            return
+        self.h.zero_()
+        rh = self.RH.view(B, T * Hp)
+        for t in range(T):
+            self.gemm(self.h, Hp, self.Wh, 2 * Hp, self.zh, 2 * Hp, B, 2 * Hp, Hp)
+            if self.gru:
+                check(lib.cham_gru_point_gates_fwd(ptr(self.xproj), ptr(self.zh), ptr(self.seq_len), B, T, t, Hp, ptr(self.h), ptr(self.hprev),
+                                                   ptr(self.G), ptr(self.R), ptr(self.RH), st), "cham_gru_point_gates_fwd")
+                self.gemm(rh[:, t * Hp:], T * Hp, self.Wch, Hp, self.zc, Hp, B, Hp, Hp)
+                check(lib.cham_gru_point_out_fwd(ptr(self.xproj), ptr(self.zc), ptr(self.seq_len), B, T, t, Hp, ptr(self.G), ptr(self.hprev),
+                                                 ptr(self.h), ptr(self.out), ptr(self.Cc), st), "cham_gru_point_out_fwd")
+            else:
+                check(lib.cham_ugrnn_point_fwd(ptr(self.xproj), ptr(self.zh), ptr(self.seq_len), B, T, t, Hp, ptr(self.h), ptr(self.out),
+                                               ptr(self.hprev), ptr(self.G), ptr(self.Cc), st), "cham_ugrnn_point_fwd")
+
+    def backward(self):
+        lib, B, T, Hp, st = self.lib, self.B, self.T, self.Hp, torch.cuda.current_stream().cuda_stream
+        if not self.step:
+            check(lib.cham_transpose_f32(ptr(self.Wh), Hp, 2 * Hp, ptr(self.WhT), st), "cham_transpose_f32")
+            if self.gru:
+                check(lib.cham_transpose_f32(ptr(self.Wch), Hp, Hp, self.WhT[2 * Hp:].data_ptr(), st), "cham_transpose_f32")
+            check(lib.cham_rnn_bwd(1 if self.gru else 0, ptr(self.dout), ptr(self.WhT), ptr(self.seq_len), B, T, Hp, ptr(self.hprev), ptr(self.G),
+                                   ptr(self.Cc), ptr(self.R) if self.gru else None, ptr(self.dxproj), st), "cham_rnn_bwd")
+            return
+        self.carry.zero_()
+        for t in range(T - 1, -1, -1):
+            if self.gru:
+                check(lib.cham_gru_point_c_bwd(ptr(self.dout), ptr(self.carry), ptr(self.seq_len), B, T, t, Hp, ptr(self.hprev), ptr(self.G),
+                                               ptr(self.Cc), ptr(self.dxproj), ptr(self.dzc), ptr(self.dzs), ptr(self.direct), st),
+                      "cham_gru_point_c_bwd")
+                self.gemm(self.dzc, Hp, self.Wch, Hp, self.drh, Hp, B, Hp, Hp, transB=1)
+                check(lib.cham_gru_point_r_bwd(ptr(self.drh), ptr(self.seq_len), B, T, t, Hp, ptr(self.hprev), ptr(self.R), ptr(self.dxproj),
+                                               ptr(self.dzs), ptr(self.direct), st), "cham_gru_point_r_bwd")
+            else:
+                check(lib.cham_ugrnn_point_bwd(ptr(self.dout), ptr(self.carry), ptr(self.seq_len), B, T, t, Hp, ptr(self.hprev), ptr(self.G),
+                                               ptr(self.Cc), ptr(self.dxproj), ptr(self.dzs), ptr(self.direct), st), "cham_ugrnn_point_bwd")
+            self.carry.copy_(self.direct)
+            self.gemm(self.dzs, 2 * Hp, self.Wh, 2 * Hp, self.carry, Hp, B, Hp, 2 * Hp, transB=1, accumulate=1)
+
+    def timed(self, iters):
+        """Device-event times (ms) of `iters` forward + backward passes."""
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for a, b in ev:
+            a.record()
+            self.forward(); self.backward()
+            b.record()
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) for a, b in ev]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=256)
+    ap.add_argument('--seq', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--small_batch', type=int, default=32)
+    ap.add_argument('--out', default=None, help="also write the JSON lines and the table to this file")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_rnn_stepwise.py needs a ROCm device: a time taken elsewhere says nothing")
+    dev = torch.device('cuda:0')
+    lib = _lib.load()
+    stacks = {(c, Hp, B): Stack(lib, c, Hp, B, a.seq, dev) for c, Hp in CASES for B in (a.batch, a.small_batch)}
+    for s in stacks.values():
+        s.timed(a.warmup)
+        assert torch.isfinite(s.dxproj).all() and torch.isfinite(s.out).all() and float(s.dxproj.abs().max()) > 0
+    times = {k: [] for k in stacks}
+    for _ in range(a.rounds):
+        for k, s in stacks.items():
+            times[k] += s.timed(a.iters)
+    lines, rows = [], []
+    for c, Hp in CASES:
+        t, ts = np.asarray(times[(c, Hp, a.batch)]), np.asarray(times[(c, Hp, a.small_batch)])
+        s = stacks[(c, Hp, a.batch)]
+        rec = dict(cell=c, Hp=Hp, path='step-wise' if s.step else 'fused', B=a.batch, T=a.seq, n=len(t), median_ms=round(float(np.median(t)), 4),
+                   min_ms=round(float(t.min()), 4), max_ms=round(float(t.max()), 4), launches_per_step_fwd=s.launches[0],
+                   launches_per_step_bwd=s.launches[1], small_B=a.small_batch, small_B_median_ms=round(float(np.median(ts)), 4))
+        if s.step:
+            rec['us_per_launch'] = round(1e3 * rec['median_ms'] / (a.seq * sum(s.launches)), 2)
+        lines.append(json.dumps(rec))
+        rows.append(rec)
+    table = ["| cell | Hp | path | launches / step (fwd + bwd) | median ms | min | max | median ms at B %d |" % a.small_batch,
+             "|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        table.append("| %s | %d | %s | %s | %.3f | %.3f | %.3f | %.3f |" % (
+            r['cell'], r['Hp'], r['path'], ("%d + %d" % (r['launches_per_step_fwd'], r['launches_per_step_bwd'])) if r['path'] == 'step-wise' else '-',
+            r['median_ms'], r['min_ms'], r['max_ms'], r['small_B_median_ms']))
+    text = "\n".join(lines + [""] + table + ["", "device: %s; B %d, T %d, %d warm-up + %d x %d timed passes per case" % (
+        torch.cuda.get_device_name(0), a.batch, a.seq, a.warmup, a.rounds, a.iters)])
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
