@@ -149,8 +149,8 @@ class Estimator:
             self._last_ckpt_time = time.time()
 
     def _coop_timed_out_local(self):
-        rt = self._store.get('runtime')
-        return bool(rt is not None and getattr(rt, '_rnn_coop_ws', None) and rt.rnn_coop_timed_out())
+        query = getattr(self._store.get('runtime'), 'rnn_coop_timed_out', None)      # (no cooperative step so far: False without a synchronisation)
+        return bool(query is not None and query())
 
     _HEALTH_MSG = ("a cooperative recurrent kernel (csrc/rnn_coop.hip) gave up a bounded spin%s: the hidden states of at least one "
                    "step are invalid.  Is another process running cooperative kernels on this GPU?")

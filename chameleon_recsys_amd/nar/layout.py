@@ -30,6 +30,12 @@ def ceil_to(x, m):
     return ((x + m - 1) // m) * m
 
 
+def rnn_stepwise(rnn_cell, Hp):
+    """Is the padded width Hp beyond the fused recurrent kernels' LDS budget (UGRNN Hp 512, GRU Hp 384)?  Then a time step is a GEMM + a
+    pointwise kernel (GRU: two of each; nar/recurrent.py)."""
+    return Hp > 512 or (rnn_cell == 'gru' and Hp > 384)
+
+
 class Entry:
     __slots__ = ("name", "shape", "offset", "size", "reg", "init", "fan")
 
@@ -52,8 +58,7 @@ class ParamLayout:
             raise ValueError("CAR_embedding_size must be a multiple of 4")
         self.H = H = rnn_units
         self.Hp = Hp = ceil_to(H, 128)
-        # beyond the fused kernels' LDS budget (UGRNN Hp 512, GRU Hp 384): GEMM + pointwise kernel per time step (GRU: two of each)
-        self.rnn_stepwise = Hp > 512 or (rnn_cell == 'gru' and Hp > 384)
+        self.rnn_stepwise = rnn_stepwise(rnn_cell, Hp)
         self.L = rnn_num_layers
         self.cell = rnn_cell
         if rnn_cell not in ('ugrnn', 'gru'):

@@ -22,6 +22,7 @@ from .. import _roctx
 from .._lib import check, ptr
 from .candidate_rows import (ACT_LEAKY, ACT_NONE, ACT_TANH, Bf16Rows, F32Rows, H2Rows, P3Rows, blocked_plane_elements,  # noqa: F401
                              planes_from_blocked, planes_to_blocked)
+from . import recurrent
 from .clicked_items_state import lane_stream
 from .layout import COL_ITEMEMB, ParamLayout
 from .metrics import BEYOND_ACCURACY_PER_CLICK, ItemCoverage
@@ -301,12 +302,9 @@ class NARRuntime:
         #     the side lane's LAST work: the small weight / bias gradients go first and run under that dgrad.
         self.p3_w2_splits = 32
         self.w2_main_rows = 131072
-        #   * the same threshold selects the recurrent kernels: steps with at most this many candidate rows (ragged batches, the shard of
-        #     a strong-scaling rank) run the UGRNN time steps on eight cooperating workgroups per 32 sessions with W_h resident in LDS
-        #     (csrc/rnn_coop.hip: ~8 us per time step instead of ~33, but 120-155 KB of LDS per workgroup - no CU shared with a plane-GEMM
-        #     workgroup); a full batch hides the single-workgroup kernels (csrc/rnn.hip, 33 KB of LDS) behind its big GEMMs
-        self.rnn_coop_rows = 131072 if (L.cell == 'ugrnn' and L.Hp == 256 and not L.rnn_stepwise) else -1
-        self._rnn_coop_ws = {}
+        #   * the same threshold selects the recurrent kernels (nar/recurrent.py: why, and the launch paths it selects between - made on first use)
+        self.rnn_coop_rows = recurrent.default_coop_rows(L)
+        self._rnn_paths = {}
         self.presample = os.environ.get("CHAM_PRESAMPLE", "1") == "1"       # NARModuleModel.presample (A/B switch)
         self.upload_stream = lane_stream(dev, "upload")       # H2D copies of a batch on their own stream, from a page-locked staging ring
         self.pinned = _PinnedRing()
@@ -402,18 +400,19 @@ class NARRuntime:
         self.global_step = int(sd['global_step'])
         self.weights_version += 1
 
-    def rnn_coop_ws(self, B):
-        """Exchange buffers + flags of the cooperative recurrent kernels for batches of B sessions (zero-initialised once; the forward and
-        the backward of a step run on the same lane and share it)."""
-        ws = self._rnn_coop_ws.get(B)
-        if ws is None:
-            nb = int(self.lib.cham_rnn_coop_workspace_bytes(B, self.layout.Hp))
-            ws = self._rnn_coop_ws[B] = torch.zeros(nb, dtype=torch.uint8, device=self.device)
-        return ws
+    def rnn_path(self, pl):
+        """The launch path of the recurrent stack (nar/recurrent.py) for the current step of `pl` - or, for a plan under construction, the
+        path whose buffers it needs."""
+        cls = recurrent.path_class(self.layout, pl.PC, pl.B, self.rnn_coop_rows)
+        path = self._rnn_paths.get(cls)
+        if path is None:
+            path = self._rnn_paths[cls] = cls(self, self.layout)
+        return path
 
     def rnn_coop_timed_out(self):
         """True if a cooperating recurrent workgroup ever gave up a bounded spin (synchronises; tests / bench / end of Estimator.train)."""
-        return any(int(self.lib.cham_rnn_coop_timeouts(ptr(ws), B, self.layout.Hp, _stream())) != 0 for B, ws in self._rnn_coop_ws.items())
+        coop = self._rnn_paths.get(recurrent.CoopUgrnn)
+        return coop is not None and coop.timed_out(_stream())
 
     def plan(self, B, T, N, n_buf, Bg=None):
         """Buffers for one batch shape, cached: ragged hourly files produce a handful of padded lengths T.  Least-recently-used
@@ -681,12 +680,6 @@ class StepPlan:
         self.R = [f32(BT, Hp) if gru else None for _ in range(L.L)]
         self.RH = [f32(BT, Hp) if gru else None for _ in range(L.L)]
         self.drnn = f32(BT, Hp)
-        self.WhT = f32(NG * Hp, Hp)
-        if L.rnn_stepwise:
-            self.h_state, self.zh, self.carry = f32(B, Hp), f32(B, 2 * Hp), f32(B, Hp)
-            self.dzs, self.direct = f32(B, 2 * Hp), f32(B, Hp)
-            if gru:      # the candidate's recurrent product and its two gradients (zh / dzs hold the r | u columns of the gate GEMM)
-                self.zc, self.dzc, self.drh = f32(B, Hp), f32(B, Hp), f32(B, Hp)
         # FCs / scorer
         self.FC1, self.dFC1 = f32(BT, 512), f32(BT, 512)
         self.pred, self.dpred = f32(BT, C), f32(BT, C)
@@ -705,6 +698,10 @@ class StepPlan:
         self.neg_slot_c = torch.zeros(BT, N, dtype=torch.int32, device=dev)
         self.Z2f, self.rnn_c, self.drnn_c, self.dxproj_c = f32(BT, C), f32(BT, Hp), f32(BT, Hp), f32(BT, NG * Hp)
         self.pos, self.P, self.PC = None, BT, Rc         # of the current step: compaction map, valid positions, candidate rows (P * NC)
+        # ... and the launch path of its recurrent stack (nar/recurrent.py; forward() sets it, backward() reads it), which adds the buffers only
+        # that path needs to the shared ones under "RNN" above
+        self.rnn = rt.rnn_path(self)
+        self.rnn.alloc(self, f32)
         # made on first need: the event of the side lane's row grouping (training-mode forward), the item rows a data-parallel step can touch
         # (sparse modes), dropout_buffers(); nbytes: set by NARRuntime.plan once the plan is built
         self.grouped_ev = self.touched = self.Xd = None
@@ -1043,7 +1040,7 @@ class NARModuleModel:
         Rc = BT * NC; RV = 2 * BT + pmax + 1
         pl.pos, pl.P, pl.PC = pos, BT, Rc
         C, Hp, Fc, Fi = L.C, L.Hp, L.Fc, L.Fi
-        cell, NGH = (1 if L.cell == 'gru' else 0), L.NG * L.Hp
+        NGH = L.NG * L.Hp
         if step is None:
             step = rt.global_step if self.is_training else self.eval_step_key(rt.global_step, self._eval_iter)
         p = rt.p
@@ -1184,35 +1181,10 @@ class NARModuleModel:
                 pl.Z2f.zero_()
                 check(lib.cham_rows_scatter(ptr(pl.Z2), ptr(pos), BT, C, ptr(pl.Z2f), _stream()), "cham_rows_scatter")
                 x = pl.Z2f
+            rnn = pl.rnn = rt.rnn_path(pl)      # the launch path of the time loops (nar/recurrent.py), decided here, once
             for l in range(L.L):
                 rt.gemm(x, p('rnn%d/Wx' % l), pl.xproj[l], BTf, NGH, K, ldx, NGH, NGH, bias=p('rnn%d/b' % l))
-                if L.rnn_stepwise and cell == 1:      # GRU: gates, then the candidate over r * h - two GEMMs + two kernels per time step
-                    pl.h_state.zero_()
-                    rh = pl.RH[l].view(B, T * Hp)
-                    for t in range(T):
-                        rt.gemm(pl.h_state, p('rnn%d/Wh' % l), pl.zh, B, 2 * Hp, Hp, Hp, 2 * Hp, 2 * Hp, force_f32=True)
-                        check(lib.cham_gru_point_gates_fwd(ptr(pl.xproj[l]), ptr(pl.zh), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.h_state),
-                                                           ptr(pl.hprev[l]), ptr(pl.G[l]), ptr(pl.R[l]), ptr(pl.RH[l]), _stream()),
-                              "cham_gru_point_gates_fwd")
-                        rt.gemm(rh[:, t * Hp:], p('rnn%d/Wch' % l), pl.zc, B, Hp, Hp, T * Hp, Hp, Hp, force_f32=True)      # RH[:, t], strided
-                        check(lib.cham_gru_point_out_fwd(ptr(pl.xproj[l]), ptr(pl.zc), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.G[l]),
-                                                         ptr(pl.hprev[l]), ptr(pl.h_state), ptr(pl.rnn_out[l]), ptr(pl.Cc[l]), _stream()),
-                              "cham_gru_point_out_fwd")
-                elif L.rnn_stepwise:    # large hidden size: one GEMM (h W_h) + one gate kernel per time step
-                    pl.h_state.zero_()
-                    for t in range(T):
-                        rt.gemm(pl.h_state, p('rnn%d/Wh' % l), pl.zh, B, 2 * Hp, Hp, Hp, 2 * Hp, 2 * Hp, force_f32=True)
-                        check(lib.cham_ugrnn_point_fwd(ptr(pl.xproj[l]), ptr(pl.zh), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.h_state),
-                                                       ptr(pl.rnn_out[l]), ptr(pl.hprev[l]), ptr(pl.G[l]), ptr(pl.Cc[l]), _stream()),
-                              "cham_ugrnn_point_fwd")
-                elif 0 < Rc <= rt.rnn_coop_rows and B <= 1024:
-                    ws = rt.rnn_coop_ws(B)
-                    check(lib.cham_ugrnn_fwd_coop(ptr(pl.xproj[l]), ptr(p('rnn%d/Wh' % l)), ptr(pl.seq_len), B, T, Hp, ptr(pl.rnn_out[l]),
-                                                  ptr(pl.hprev[l]), ptr(pl.G[l]), ptr(pl.Cc[l]), ptr(ws), ws.numel(), _stream()), "cham_ugrnn_fwd_coop")
-                else:
-                    check(lib.cham_rnn_fwd(cell, ptr(pl.xproj[l]), ptr(p('rnn%d/Wh' % l)), ptr(pl.seq_len), B, T, Hp,
-                                           ptr(pl.rnn_out[l]), ptr(pl.hprev[l]), ptr(pl.G[l]), ptr(pl.Cc[l]), ptr(pl.R[l]),
-                                           ptr(pl.RH[l]), _stream()), "cham_rnn_fwd")
+                rnn.forward(pl, l, _stream())
                 x, ldx, K = pl.rnn_out[l], Hp, Hp
                 if drop:     # DropoutWrapper(output_keep_prob), nar_model.py:1331: the layer's OUTPUT is dropped, its state is not
                     dropout(pl.rnn_out[l], pl.rnn_drop[l], BTf, Hp, Hp, 20 + l, 20 + l, 1, None)
@@ -1371,6 +1343,7 @@ class NARModuleModel:
         deferred_w2 = None
         with side(e_dZ2c):
             ss = _stream()
+            rnn = pl.rnn                 # the launch path of the time loops, as forward() chose it (nar/recurrent.py)
             rnn_y = (lambda l: pl.rnn_drop[l]) if drop else (lambda l: pl.rnn_out[l])     # what the next layer / FC1 consumed
 
             def fc_wgrads():
@@ -1396,37 +1369,7 @@ class NARModuleModel:
             if drop:
                 dropout(pl.drnn, pl.drnn, BTf, Hp, Hp, 20 + last, 20 + last, 1, None)
             for l in range(last, -1, -1):
-                if L.rnn_stepwise and cell == 1:
-                    pl.carry.zero_()
-                    for t in range(T - 1, -1, -1):
-                        check(lib.cham_gru_point_c_bwd(ptr(pl.drnn), ptr(pl.carry), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.hprev[l]),
-                                                       ptr(pl.G[l]), ptr(pl.Cc[l]), ptr(pl.dxproj), ptr(pl.dzc), ptr(pl.dzs), ptr(pl.direct),
-                                                       ss), "cham_gru_point_c_bwd")
-                        rt.gemm(pl.dzc, p('rnn%d/Wch' % l), pl.drh, B, Hp, Hp, Hp, Hp, Hp, transB=1, force_f32=True)     # d(r h) = dzc W_ch^T
-                        check(lib.cham_gru_point_r_bwd(ptr(pl.drh), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.hprev[l]), ptr(pl.R[l]),
-                                                       ptr(pl.dxproj), ptr(pl.dzs), ptr(pl.direct), ss), "cham_gru_point_r_bwd")
-                        # carry = direct + [dz_r | dz_u] W_gh^T  (rows beyond their length: dzs = 0, direct = carry -> unchanged)
-                        pl.carry.copy_(pl.direct)
-                        rt.gemm(pl.dzs, p('rnn%d/Wh' % l), pl.carry, B, Hp, 2 * Hp, 2 * Hp, 2 * Hp, Hp, transB=1, accumulate=1, force_f32=True)
-                elif L.rnn_stepwise:
-                    pl.carry.zero_()
-                    for t in range(T - 1, -1, -1):
-                        check(lib.cham_ugrnn_point_bwd(ptr(pl.drnn), ptr(pl.carry), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.hprev[l]),
-                                                       ptr(pl.G[l]), ptr(pl.Cc[l]), ptr(pl.dxproj), ptr(pl.dzs), ptr(pl.direct), ss),
-                              "cham_ugrnn_point_bwd")
-                        # carry = direct + dzs W_h^T  (rows beyond their length: dzs = 0, direct = carry -> unchanged)
-                        pl.carry.copy_(pl.direct)
-                        rt.gemm(pl.dzs, p('rnn%d/Wh' % l), pl.carry, B, Hp, 2 * Hp, 2 * Hp, 2 * Hp, Hp, transB=1, accumulate=1, force_f32=True)
-                elif 0 < Rc <= rt.rnn_coop_rows and B <= 1024:
-                    ws = rt.rnn_coop_ws(B)
-                    check(lib.cham_ugrnn_bwd_coop(ptr(pl.drnn), ptr(p('rnn%d/Wh' % l)), ptr(pl.seq_len), B, T, Hp, ptr(pl.hprev[l]), ptr(pl.G[l]),
-                                                  ptr(pl.Cc[l]), ptr(pl.dxproj), ptr(ws), ws.numel(), ss), "cham_ugrnn_bwd_coop")
-                else:
-                    check(lib.cham_transpose_f32(ptr(p('rnn%d/Wh' % l)), Hp, 2 * Hp, ptr(pl.WhT), ss), "cham_transpose_f32")
-                    if cell == 1:
-                        check(lib.cham_transpose_f32(ptr(p('rnn%d/Wch' % l)), Hp, Hp, pl.WhT[2 * Hp:].data_ptr(), ss), "cham_transpose_f32")
-                    check(lib.cham_rnn_bwd(cell, ptr(pl.drnn), ptr(pl.WhT), ptr(pl.seq_len), B, T, Hp, ptr(pl.hprev[l]), ptr(pl.G[l]),
-                                           ptr(pl.Cc[l]), ptr(pl.R[l]), ptr(pl.dxproj), ss), "cham_rnn_bwd")
+                rnn.backward(pl, l, ss)
                 if l == 0:   # -> gradient w.r.t. the CAR tanh pre-activation of the clicked-input rows (main lane waits for it)
                     dxp = pl.dxproj
                     if pos is not None:
@@ -1448,8 +1391,7 @@ class NARModuleModel:
                                 fc_wgrads()
                             arm.b2_grad(pl)
                             rt.gemm(pl.Z2, dxp, g('rnn0/Wx'), C, NGH, BT, C, NGH, NGH, transA=1, splits=0)
-                            rt.gemm(pl.hprev[0], pl.dxproj, g('rnn0/Wh'), Hp, 2 * Hp, BTf, Hp, NGH, 2 * Hp, transA=1, splits=0, force_f32=True)
-                            rt.colsum(pl.dxproj, NGH, BTf, NGH, g('rnn0/b'))
+                            rnn.wgrads(pl, 0)
                             e_auxdone = mark()
                         rt.side_stream.wait_event(e_cdgrad)
                         arm.w2_wgrad(pl, rt.p3_w2_splits)
@@ -1484,11 +1426,7 @@ class NARModuleModel:
                     rt.gemm(rnn_y(l - 1), pl.dxproj, g('rnn%d/Wx' % l), Hp, NGH, BTf, Hp, NGH, NGH, transA=1, splits=0)
                     if drop:
                         dropout(pl.drnn, pl.drnn, BTf, Hp, Hp, 20 + l - 1, 20 + l - 1, 1, None)
-                # recurrent weights: their forward product runs in the fp32 time-step kernel -> fp32 wgrad in every mode
-                rt.gemm(pl.hprev[l], pl.dxproj, g('rnn%d/Wh' % l), Hp, 2 * Hp, BTf, Hp, NGH, 2 * Hp, transA=1, splits=0, force_f32=True)
-                if cell == 1:   # candidate kernel: (r * h_prev)^T dz_c
-                    rt.gemm(pl.RH[l], pl.dxproj[:, 2 * Hp:], g('rnn%d/Wch' % l), Hp, Hp, BTf, Hp, NGH, Hp, transA=1, splits=0, force_f32=True)
-                rt.colsum(pl.dxproj, NGH, BTf, NGH, g('rnn%d/b' % l))
+                rnn.wgrads(pl, l)
             if deferred_w2 is not None:
                 deferred_w2()
         def precar_backward(ws):

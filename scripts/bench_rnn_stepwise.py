@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Time of the recurrent stack alone, forward + backward of one layer, as nar_model.py launches it: the step-wise GRU (rnn_units above
-384) next to the step-wise UGRNN and the fused GRU.  Full-length sessions; the x W_x projection and the weight gradients are not part of
-it (they are the same GEMMs for every path).
+"""Time of the recurrent stack alone, forward + backward of one layer, through the model's own launch paths (nar/recurrent.py): the
+step-wise GRU (rnn_units above 384) next to the step-wise UGRNN and the fused GRU.  Full-length sessions; the x W_x projection and the
+weight gradients are not part of it (they are the same GEMMs for every path).
 
   python scripts/bench_rnn_stepwise.py [--batch 256] [--seq 20] [--warmup 5] [--iters 20] [--rounds 3] [--out FILE]
 
@@ -13,6 +13,7 @@ import argparse
 import json
 import os
 import sys
+import types
 
 import numpy as np
 import torch
@@ -22,93 +23,50 @@ sys.path.insert(0, ROOT)
 
 from chameleon_recsys_amd import _lib                     # noqa: E402
 from chameleon_recsys_amd._lib import check, ptr         # noqa: E402
+from chameleon_recsys_amd.nar import recurrent            # noqa: E402
+from chameleon_recsys_amd.nar.layout import rnn_stepwise  # noqa: E402
 
 CASES = [('gru', 512), ('gru', 1024), ('ugrnn', 640), ('ugrnn', 1024), ('gru', 384)]
 
 
-def stepwise(cell, Hp):
-    """ParamLayout.rnn_stepwise."""
-    return Hp > 512 or (cell == 'gru' and Hp > 384)
-
-
 class Stack:
-    """Buffers of one recurrent layer and the launch sequence of nar_model.py's forward / backward for it."""
+    """One recurrent layer as nar/recurrent.py sees it: the stub HOST of a launch path (lib, gemm, p) and its PLAN (the buffers, under
+    StepPlan's names) in one object, driving the path class the model's own selection picks for the width."""
 
     def __init__(self, lib, cell, Hp, B, T, dev, seed=0):
-        self.lib, self.cell, self.Hp, self.B, self.T = lib, cell, Hp, B, T
-        self.gru, self.step = cell == 'gru', stepwise(cell, Hp)
-        ng = 3 if self.gru else 2
+        self.lib, self.cell, self.Hp, self.B, self.T, self.BT = lib, cell, Hp, B, T, B * T
+        gru = cell == 'gru'
+        ng = 3 if gru else 2
+        L = types.SimpleNamespace(cell=cell, Hp=Hp, NG=ng, rnn_stepwise=rnn_stepwise(cell, Hp))
         g = torch.Generator(device=dev)
         g.manual_seed(seed + Hp)
         rnd = lambda *s: torch.randn(*s, generator=g, device=dev, dtype=torch.float32)
         f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         # W_gh [Hp, 2Hp] directly followed by W_ch [Hp, Hp], as the flat parameter buffer holds them
-        self.W = rnd(Hp * (3 if self.gru else 2) * Hp) * Hp ** -0.5
-        self.Wh, self.Wch = self.W[:2 * Hp * Hp].view(Hp, 2 * Hp), (self.W[2 * Hp * Hp:].view(Hp, Hp) if self.gru else None)
-        self.WhT = f32(ng * Hp, Hp)
-        self.xproj, self.dout = 0.7 * rnd(B * T, ng * Hp), rnd(B * T, Hp)
+        W = rnd(Hp * ng * Hp) * Hp ** -0.5
+        self.weights = {'rnn0/Wh': W[:2 * Hp * Hp].view(Hp, 2 * Hp), 'rnn0/Wch': W[2 * Hp * Hp:].view(Hp, Hp) if gru else None}
+        self.p = self.weights.__getitem__
+        self.xproj, self.drnn = [0.7 * rnd(B * T, ng * Hp)], rnd(B * T, Hp)
         self.seq_len = torch.full((B,), T, dtype=torch.int32, device=dev)
-        self.out, self.hprev, self.G, self.Cc, self.R, self.RH = (f32(B * T, Hp) for _ in range(6))
+        self.rnn_out, self.hprev, self.G, self.Cc = ([f32(B * T, Hp)] for _ in range(4))
+        self.R, self.RH = ([f32(B * T, Hp) if gru else None] for _ in range(2))
         self.dxproj = f32(B * T, ng * Hp)
-        self.h, self.zh, self.carry, self.dzs, self.direct = f32(B, Hp), f32(B, 2 * Hp), f32(B, Hp), f32(B, 2 * Hp), f32(B, Hp)
-        self.zc, self.dzc, self.drh = f32(B, Hp), f32(B, Hp), f32(B, Hp)
-        # launches per time step (forward, backward): GEMMs + kernels (+ the carry copy)
-        self.launches = ((4, 5) if self.gru else (2, 3)) if self.step else (0, 0)
+        # (PC 0: a step without candidate rows - never the cooperative path, which is not a case here)
+        self.path = recurrent.path_class(L, 0, B, recurrent.default_coop_rows(L))(self, L)
+        self.path.alloc(self, f32)
+        self.step, self.launches = L.rnn_stepwise, self.path.launches_per_step or (0, 0)
 
-    def gemm(self, A, lda, Bm, ldb, C, ldc, M, N, K, transB=0, accumulate=0):
+    def gemm(self, A, Bm, C, M, N, K, lda, ldb, ldc, transB=0, accumulate=0, force_f32=True):
         check(self.lib.cham_gemm_f32(ptr(A), lda, 0, ptr(Bm), ldb, transB, ptr(C), ldc, M, N, K, None, 0, None, 0, 0, None, 0, 1, accumulate,
                                      None, 0, 1, torch.cuda.current_stream().cuda_stream), "cham_gemm_f32")
-
-    def forward(self):
-        lib, B, T, Hp, st = self.lib, self.B, self.T, self.Hp, torch.cuda.current_stream().cuda_stream
-        if not self.step:
-            check(lib.cham_rnn_fwd(1 if self.gru else 0, ptr(self.xproj), ptr(self.W), ptr(self.seq_len), B, T, Hp, ptr(self.out), ptr(self.hprev),
-                                   ptr(self.G), ptr(self.Cc), ptr(self.R) if self.gru else None, ptr(self.RH) if self.gru else None, st), "cham_rnn_fwd")
-            return
-        self.h.zero_()
-        rh = self.RH.view(B, T * Hp)
-        for t in range(T):
-            self.gemm(self.h, Hp, self.Wh, 2 * Hp, self.zh, 2 * Hp, B, 2 * Hp, Hp)
-            if self.gru:
-                check(lib.cham_gru_point_gates_fwd(ptr(self.xproj), ptr(self.zh), ptr(self.seq_len), B, T, t, Hp, ptr(self.h), ptr(self.hprev),
-                                                   ptr(self.G), ptr(self.R), ptr(self.RH), st), "cham_gru_point_gates_fwd")
-                self.gemm(rh[:, t * Hp:], T * Hp, self.Wch, Hp, self.zc, Hp, B, Hp, Hp)
-                check(lib.cham_gru_point_out_fwd(ptr(self.xproj), ptr(self.zc), ptr(self.seq_len), B, T, t, Hp, ptr(self.G), ptr(self.hprev),
-                                                 ptr(self.h), ptr(self.out), ptr(self.Cc), st), "cham_gru_point_out_fwd")
-            else:
-                check(lib.cham_ugrnn_point_fwd(ptr(self.xproj), ptr(self.zh), ptr(self.seq_len), B, T, t, Hp, ptr(self.h), ptr(self.out),
-                                               ptr(self.hprev), ptr(self.G), ptr(self.Cc), st), "cham_ugrnn_point_fwd")
-
-    def backward(self):
-        lib, B, T, Hp, st = self.lib, self.B, self.T, self.Hp, torch.cuda.current_stream().cuda_stream
-        if not self.step:
-            check(lib.cham_transpose_f32(ptr(self.Wh), Hp, 2 * Hp, ptr(self.WhT), st), "cham_transpose_f32")
-            if self.gru:
-                check(lib.cham_transpose_f32(ptr(self.Wch), Hp, Hp, self.WhT[2 * Hp:].data_ptr(), st), "cham_transpose_f32")
-            check(lib.cham_rnn_bwd(1 if self.gru else 0, ptr(self.dout), ptr(self.WhT), ptr(self.seq_len), B, T, Hp, ptr(self.hprev), ptr(self.G),
-                                   ptr(self.Cc), ptr(self.R) if self.gru else None, ptr(self.dxproj), st), "cham_rnn_bwd")
-            return
-        self.carry.zero_()
-        for t in range(T - 1, -1, -1):
-            if self.gru:
-                check(lib.cham_gru_point_c_bwd(ptr(self.dout), ptr(self.carry), ptr(self.seq_len), B, T, t, Hp, ptr(self.hprev), ptr(self.G),
-                                               ptr(self.Cc), ptr(self.dxproj), ptr(self.dzc), ptr(self.dzs), ptr(self.direct), st),
-                      "cham_gru_point_c_bwd")
-                self.gemm(self.dzc, Hp, self.Wch, Hp, self.drh, Hp, B, Hp, Hp, transB=1)
-                check(lib.cham_gru_point_r_bwd(ptr(self.drh), ptr(self.seq_len), B, T, t, Hp, ptr(self.hprev), ptr(self.R), ptr(self.dxproj),
-                                               ptr(self.dzs), ptr(self.direct), st), "cham_gru_point_r_bwd")
-            else:
-                check(lib.cham_ugrnn_point_bwd(ptr(self.dout), ptr(self.carry), ptr(self.seq_len), B, T, t, Hp, ptr(self.hprev), ptr(self.G),
-                                               ptr(self.Cc), ptr(self.dxproj), ptr(self.dzs), ptr(self.direct), st), "cham_ugrnn_point_bwd")
-            self.carry.copy_(self.direct)
-            self.gemm(self.dzs, 2 * Hp, self.Wh, 2 * Hp, self.carry, Hp, B, Hp, 2 * Hp, transB=1, accumulate=1)
 
     def timed(self, iters):
         """Device-event times (ms) of `iters` forward + backward passes."""
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
         for a, b in ev:
             a.record()
-            self.forward(); self.backward()
+            st = torch.cuda.current_stream().cuda_stream
+            self.path.forward(self, 0, st); self.path.backward(self, 0, st)
             b.record()
         torch.cuda.synchronize()
         return [a.elapsed_time(b) for a, b in ev]
@@ -131,7 +89,7 @@ def main():
     stacks = {(c, Hp, B): Stack(lib, c, Hp, B, a.seq, dev) for c, Hp in CASES for B in (a.batch, a.small_batch)}
     for s in stacks.values():
         s.timed(a.warmup)
-        assert torch.isfinite(s.dxproj).all() and torch.isfinite(s.out).all() and float(s.dxproj.abs().max()) > 0
+        assert torch.isfinite(s.dxproj).all() and torch.isfinite(s.rnn_out[0]).all() and float(s.dxproj.abs().max()) > 0
     times = {k: [] for k in stacks}
     for _ in range(a.rounds):
         for k, s in stacks.items():

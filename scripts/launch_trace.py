@@ -1,5 +1,6 @@
 """Launch trace of the training step (manual tool, not a test): proves that a change of the step DRIVER - the schedule in
-NARModuleModel._forward / backward, an arm of nar/candidate_rows.py - left every launch, its order, its arguments and its lane as they were.
+NARModuleModel._forward / backward, an arm of nar/candidate_rows.py, a launch path of nar/recurrent.py - left every launch, its order, its
+arguments and its lane as they were.
 
 One configuration per process (the switches are read when the library / the runtime is created), traced under both schedules:
   short   as is: at these shapes Rc <= rt.w2_main_rows - W2 weight gradient on the main lane, cooperative recurrent kernels, no head split
@@ -43,6 +44,11 @@ CONFIGS = {
     'neg10': ({}, {'neg': 10}, {}, 'g1', 0),
     'neg10_bf16': ({}, {'neg': 10, 'gemm_dtype': 'bf16'}, {}, 'g1', 0),
     'gru2': ({}, {'rnn_cell': 'gru', 'rnn_num_layers': 2}, {}, 'g1', 0),
+    'ugrnn2': ({}, {'rnn_num_layers': 2}, {}, 'g1', 0),                                    # two layers: no third lane for the small weight gradients
+    'ugrnn_wide': ({}, {'H': 600}, {}, 'g1', 0),                                           # Hp 640: step-wise UGRNN
+    'gru_wide': ({}, {'rnn_cell': 'gru', 'H': 500}, {}, 'g1', 0),                          # Hp 512: step-wise GRU
+    'gru_wide2': ({}, {'rnn_cell': 'gru', 'H': 400, 'rnn_num_layers': 2}, {}, 'g1', 0),
+    'gru_dropout': ({}, {'rnn_cell': 'gru', 'H': 500, 'dropout_keep_prob': 0.8}, {}, 'g1', 0),
     'full_length': ({}, {}, {}, 'full', 0),
     'microbatched': ({}, {}, {}, 'g1', 8),
 }
