@@ -104,6 +104,8 @@ _SIGNATURES = {
     "cham_gru_point_out_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
     "cham_gru_point_c_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
     "cham_gru_point_r_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
+    "cham_lstm_point_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P]),
+    "cham_lstm_point_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
     "cham_transpose_f32": (c_int, [P, c_int, c_int, P, P]),
     "cham_rows_gather": (c_int, [P, P, c_long, c_int, P, P]),
     "cham_rows_scatter": (c_int, [P, P, c_long, c_int, P, P]),

@@ -1,4 +1,5 @@
-// Recurrent session encoder time-step kernels (UGRNN = the reference's cell; GRU selectable: cell_kind 1).
+// Recurrent session encoder time-step kernels (UGRNN = the reference's cell; GRU selectable: cell_kind 1; LSTM: step-wise point kernels only,
+// at the end of this file).
 //
 // Replaces nar_module/nar/nar_model.py:1308-1361: MultiRNNCell([DropoutWrapper(UGRNNCell(H))]) unrolled by
 // tf.nn.dynamic_rnn(sequence_length).  UGRNN step (tf.contrib.rnn.UGRNNCell, TF r1.12):
@@ -580,7 +581,8 @@ extern "C" int cham_rnn_bwd(int cell_kind, const float* dout, const float* WhT, 
 // the reference's hypertuning searches rnn_units up to 1024, nar_mlengine_hypertuning.yaml:28-33): the host runs the
 // recurrent products h W_h as GEMM launches per time step (csrc/gemm.hip) and these kernels do the gate arithmetic,
 // length masking and state carry.  zh = h_{t-1} W_h for the step (UGRNN: [B, 2Hp]; GRU gates: [B, 2Hp], candidate: [B, Hp]).
-// UGRNN: one GEMM + one kernel per step and direction (k_ugrnn_point_*); GRU: two of each (k_gru_point_*, further down).
+// UGRNN: one GEMM + one kernel per step and direction (k_ugrnn_point_*); GRU: two of each (k_gru_point_*, further down); the LSTM has no
+// fused time loop and runs like the UGRNN at every width (k_lstm_point_*, at the end).
 // Every saved plane is written at every t, also beyond a session's length, as the fused kernels do; one thread per (b, hidden)
 // element, plain stores, no atomics: two runs are bit-identical.
 __global__ __launch_bounds__(256) void k_ugrnn_point_fwd(const float* __restrict__ xproj, const float* __restrict__ zh,
@@ -744,3 +746,84 @@ extern "C" int cham_gru_point_r_bwd(const float* drh, const int32_t* seq_len, in
     return CHAM_OK;
 }
 #undef GRU_POINT_BAD_DIMS
+
+// LSTM step-wise (tf.nn.rnn_cell.LSTMCell, TF r1.12 defaults: no peepholes / projection / clipping, forget_bias 1): the UGRNN's shape - one
+// gate GEMM zh [B,4Hp] = h W_h and one kernel per step forward, one kernel + copy + accumulating GEMM backward.  Column blocks of xproj,
+// zh, dxproj and dzs in TF's order i | j | f | o.  The cell state c and its gradient are element-wise: they live in these kernels only.
+//   i = s(z_i)  j = tanh(z_j)  f = s(z_f + 1)  o = s(z_o);  c' = f c + i j;  h' = o tanh(c');  beyond the length: out = 0, c and h carried
+__global__ __launch_bounds__(256) void k_lstm_point_fwd(const float* __restrict__ xproj, const float* __restrict__ zh,
+                                                        const int* __restrict__ seq_len, int B, int T, int t, int Hp,
+                                                        float* __restrict__ h /*[B,Hp] state in/out*/, float* __restrict__ c /*the same*/,
+                                                        float* __restrict__ out, float* __restrict__ hprev, float* __restrict__ cprev,
+                                                        float* __restrict__ Gi, float* __restrict__ Gj, float* __restrict__ Gf,
+                                                        float* __restrict__ Go, float* __restrict__ TC) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * Hp) return;
+    const int b = i / Hp, hid = i % Hp;
+    const size_t bt = (size_t)b * T + t, o = bt * Hp + hid;
+    const float* z = zh + (size_t)b * 4 * Hp + hid;
+    const float* x = xproj + bt * 4 * Hp + hid;
+    const float gi = sigmoidf_(z[0] + x[0]);
+    const float gj = cham_tanhf(z[Hp] + x[Hp]);
+    const float gf = sigmoidf_(z[2 * Hp] + x[2 * Hp] + 1.0f);
+    const float go = sigmoidf_(z[3 * Hp] + x[3 * Hp]);
+    const float ho = h[i], co = c[i];
+    const float cn = gf * co + gi * gj, tc = cham_tanhf(cn), hn = go * tc;
+    const bool valid = t < seq_len[b];
+    out[o] = valid ? hn : 0.f; hprev[o] = ho; cprev[o] = co;
+    Gi[o] = gi; Gj[o] = gj; Gf[o] = gf; Go[o] = go; TC[o] = tc;
+    if (valid) { h[i] = hn; c[i] = cn; }
+}
+// dh = dout[:,t] + carry_h;  dc = carry_c + dh o (1 - tc^2);  dz -> dxproj[:,t] and dzs [B,4Hp] (for carry_h = direct + dzs W_h^T, a GEMM);
+// carry_c = dc f in place;  direct [B,Hp] = 0.  Beyond the length: dz = 0, direct = carry_h, carry_c unchanged.
+__global__ __launch_bounds__(256) void k_lstm_point_bwd(const float* __restrict__ dout, const float* __restrict__ carry_h,
+                                                        float* __restrict__ carry_c, const int* __restrict__ seq_len, int B, int T, int t,
+                                                        int Hp, const float* __restrict__ cprev, const float* __restrict__ Gi,
+                                                        const float* __restrict__ Gj, const float* __restrict__ Gf,
+                                                        const float* __restrict__ Go, const float* __restrict__ TC,
+                                                        float* __restrict__ dxproj, float* __restrict__ dzs, float* __restrict__ direct) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * Hp) return;
+    const int b = i / Hp, hid = i % Hp;
+    const size_t bt = (size_t)b * T + t, o = bt * Hp + hid;
+    float dzi = 0.f, dzj = 0.f, dzf = 0.f, dzo = 0.f, dd = carry_h[i];          // beyond the session's length both carries pass through unchanged
+    if (t < seq_len[b]) {
+        const float dh = dout[o] + carry_h[i];
+        const float gi = Gi[o], gj = Gj[o], gf = Gf[o], go = Go[o], tc = TC[o];
+        const float dc = carry_c[i] + dh * go * (1.f - tc * tc);
+        dzi = dc * gj * gi * (1.f - gi);
+        dzj = dc * gi * (1.f - gj * gj);
+        dzf = dc * cprev[o] * gf * (1.f - gf);
+        dzo = dh * tc * go * (1.f - go);
+        carry_c[i] = dc * gf;
+        dd = 0.f;                                                               // h reaches h' through the gate product only
+    }
+    float* dx = dxproj + bt * 4 * Hp + hid;
+    float* dz = dzs + (size_t)b * 4 * Hp + hid;
+    dx[0] = dzi; dx[Hp] = dzj; dx[2 * Hp] = dzf; dx[3 * Hp] = dzo;
+    dz[0] = dzi; dz[Hp] = dzj; dz[2 * Hp] = dzf; dz[3 * Hp] = dzo;
+    direct[i] = dd;
+}
+#define LSTM_POINT_BAD_DIMS (B <= 0 || T <= 0 || Hp <= 0 || t < 0 || t >= T)
+extern "C" int cham_lstm_point_fwd(const float* xproj, const float* zh, const int32_t* seq_len, int B, int T, int t, int Hp, float* h,
+                                   float* c, float* out, float* hprev, float* cprev, float* Gi, float* Gj, float* Gf, float* Go,
+                                   float* TC, void* stream) {
+    if (!xproj || !zh || !seq_len || !h || !c || !out || !hprev || !cprev || !Gi || !Gj || !Gf || !Go || !TC || LSTM_POINT_BAD_DIMS)
+        return -CHAM_ERR_ARG;
+    hipLaunchKernelGGL(k_lstm_point_fwd, dim3((B * Hp + 255) / 256), dim3(256), 0, (hipStream_t)stream, xproj, zh, seq_len, B, T, t, Hp,
+                       h, c, out, hprev, cprev, Gi, Gj, Gf, Go, TC);
+    CHAM_CHECK_LAUNCH();
+    return CHAM_OK;
+}
+extern "C" int cham_lstm_point_bwd(const float* dout, const float* carry_h, float* carry_c, const int32_t* seq_len, int B, int T, int t,
+                                   int Hp, const float* cprev, const float* Gi, const float* Gj, const float* Gf, const float* Go,
+                                   const float* TC, float* dxproj, float* dzs, float* direct, void* stream) {
+    if (!dout || !carry_h || !carry_c || !seq_len || !cprev || !Gi || !Gj || !Gf || !Go || !TC || !dxproj || !dzs || !direct ||
+        LSTM_POINT_BAD_DIMS)
+        return -CHAM_ERR_ARG;
+    hipLaunchKernelGGL(k_lstm_point_bwd, dim3((B * Hp + 255) / 256), dim3(256), 0, (hipStream_t)stream, dout, carry_h, carry_c, seq_len,
+                       B, T, t, Hp, cprev, Gi, Gj, Gf, Go, TC, dxproj, dzs, direct);
+    CHAM_CHECK_LAUNCH();
+    return CHAM_OK;
+}
+#undef LSTM_POINT_BAD_DIMS

@@ -3,7 +3,7 @@ feature-column descriptors, and conversion to / from the reference's logical var
 
 Logical variable inventory: nar_module/nar/nar_model.py (scopes under ``main/``):
   :736-742 ``{name}_cat_embedding``, :911-919 ``items_embedding``, :890-898 ``gamma_scale/beta_center``,
-  :375-388 PreCAR/CAR Dense, :1317 UGRNNCell kernel/bias, :411-426 FC1/FC2, :447-473 matching_dense_layer_1..4.
+  :375-388 PreCAR/CAR Dense, :1315-1317 UGRNNCell / GRUCell / LSTMCell kernel/bias, :411-426 FC1/FC2, :447-473 matching_dense_layer_1..4.
 Padding rules (MI355X): feature widths -> multiples of 4 floats (16-byte rows for float4 / global_load_dwordx4),
 rnn_units -> multiple of 128 (4 waves x 32-wide MFMA tiles); pad weights are 0 and provably stay 0.
 """
@@ -32,8 +32,8 @@ def ceil_to(x, m):
 
 def rnn_stepwise(rnn_cell, Hp):
     """Is the padded width Hp beyond the fused recurrent kernels' LDS budget (UGRNN Hp 512, GRU Hp 384)?  Then a time step is a GEMM + a
-    pointwise kernel (GRU: two of each; nar/recurrent.py)."""
-    return Hp > 512 or (rnn_cell == 'gru' and Hp > 384)
+    pointwise kernel (GRU: two of each; nar/recurrent.py).  The LSTM has no fused kernels: step-wise at every width."""
+    return Hp > 512 or (rnn_cell == 'gru' and Hp > 384) or rnn_cell == 'lstm'
 
 
 class Entry:
@@ -61,9 +61,10 @@ class ParamLayout:
         self.rnn_stepwise = rnn_stepwise(rnn_cell, Hp)
         self.L = rnn_num_layers
         self.cell = rnn_cell
-        if rnn_cell not in ('ugrnn', 'gru'):
-            raise ValueError("rnn_cell=%r: 'ugrnn' (the reference's cell, nar_model.py:1317) or 'gru'" % rnn_cell)
-        self.NG = 2 if rnn_cell == 'ugrnn' else 3          # gate/candidate column blocks of the input projection
+        if rnn_cell not in ('ugrnn', 'gru', 'lstm'):
+            raise ValueError("rnn_cell=%r: 'ugrnn' (the reference's cell, nar_model.py:1317), 'gru' or 'lstm'" % rnn_cell)
+        self.NG = {'ugrnn': 2, 'gru': 3, 'lstm': 4}[rnn_cell]          # gate/candidate column blocks of the input projection
+        NGh = 4 if rnn_cell == 'lstm' else 2               # ... and of the recurrent gate product h W_h (GRU: the candidate has W_ch)
         self.n_items = n_items
         self.D = ace_dim
         scfg = session_features_config['sequence_features']
@@ -150,7 +151,7 @@ class ParamLayout:
         ents += [Entry('b1', (C,), False, 'zeros'), Entry('b2', (C,), False, 'zeros')]
         for l in range(self.L):
             Ip = C if l == 0 else Hp
-            ents += [Entry('rnn%d/Wx' % l, (Ip, self.NG * Hp), False, 'pad'), Entry('rnn%d/Wh' % l, (Hp, 2 * Hp), False, 'pad')]
+            ents += [Entry('rnn%d/Wx' % l, (Ip, self.NG * Hp), False, 'pad'), Entry('rnn%d/Wh' % l, (Hp, NGh * Hp), False, 'pad')]
             if rnn_cell == 'gru':    # W_ch directly behind W_gh: the recurrent kernel takes ONE pointer (chameleon_nar.h)
                 ents.append(Entry('rnn%d/Wch' % l, (Hp, Hp), False, 'pad'))
             ents.append(Entry('rnn%d/b' % l, (self.NG * Hp,), False, 'zeros'))
@@ -247,6 +248,9 @@ class ParamLayout:
             if self.cell == 'ugrnn':
                 specs['rnn/%d/kernel' % l] = ((I + H, 2 * H), 'xavier', False)
                 specs['rnn/%d/bias' % l] = ((2 * H,), 'zeros', False)
+            elif self.cell == 'lstm':     # tf.nn.rnn_cell.LSTMCell variables: one kernel, column blocks i | j | f | o (forget_bias is not a variable)
+                specs['rnn/%d/kernel' % l] = ((I + H, 4 * H), 'xavier', False)
+                specs['rnn/%d/bias' % l] = ((4 * H,), 'zeros', False)
             else:     # tf.nn.rnn_cell.GRUCell variables: gates (bias init 1.0) and candidate
                 specs['rnn/%d/gates/kernel' % l] = ((I + H, 2 * H), 'xavier', False)
                 specs['rnn/%d/gates/bias' % l] = ((2 * H,), 'ones', False)
@@ -272,7 +276,7 @@ class ParamLayout:
         Scopes follow nar_model.py: "main" (:210) / "user_items_contextual_features" (:314) / "features" (:744) /
         "{name}_cat_embedding/{name}_embedding" (:737-739); "item_features" (:922) / "item_cat_embedding/items_embedding" (:913-916);
         "input_features_center_scale/{gamma_scale, beta_center}" (:890-895); "CAR/{PreCAR,CAR}_representation" (:374-387);
-        "RNN/rnn/multi_rnn_cell/cell_l/ugrnn_cell" (:1309-1342; tf.nn.rnn_cell.GRUCell: "gru_cell/{gates, candidate}");
+        "RNN/rnn/multi_rnn_cell/cell_l/ugrnn_cell" (:1309-1342; tf.nn.rnn_cell.GRUCell: "gru_cell/{gates, candidate}", LSTMCell: "lstm_cell");
         "session_representation/{FC1, FC2}" (:410-425); "recommendations_ranking/matching_dense_layer_{1..4}" (:444-472).
         tf.layers.Dense OBJECTS bind their variable scope at the first __call__, not at construction (TF 1.x base Layer._set_scope):
         PreCAR_dense is built AND first called inside "CAR" (:372-381) -> "main/CAR/PreCAR_representation"; CAR_dense is built there
@@ -298,9 +302,9 @@ class ParamLayout:
             m['main/user_personalized_contextual_article_embedding/input/CAR_representation/' + v] = 'CAR/' + v
         for l in range(self.L):
             cell = 'main/RNN/rnn/multi_rnn_cell/cell_%d/' % l
-            if self.cell == 'ugrnn':
-                m[cell + 'ugrnn_cell/kernel'] = 'rnn/%d/kernel' % l
-                m[cell + 'ugrnn_cell/bias'] = 'rnn/%d/bias' % l
+            if self.cell in ('ugrnn', 'lstm'):
+                m[cell + self.cell + '_cell/kernel'] = 'rnn/%d/kernel' % l
+                m[cell + self.cell + '_cell/bias'] = 'rnn/%d/bias' % l
             else:
                 for part in ('gates', 'candidate'):
                     m[cell + 'gru_cell/%s/kernel' % part] = 'rnn/%d/%s/kernel' % (l, part)
@@ -402,7 +406,7 @@ class ParamLayout:
         for l in range(self.L):
             I = C if l == 0 else H
             Wx, Wh, rb = v('rnn%d/Wx' % l), v('rnn%d/Wh' % l), v('rnn%d/b' % l)
-            if self.cell == 'ugrnn':
+            if self.cell in ('ugrnn', 'lstm'):
                 K = np.asarray(logical['rnn/%d/kernel' % l]); bb = np.asarray(logical['rnn/%d/bias' % l])
             else:
                 K = np.asarray(logical['rnn/%d/gates/kernel' % l]); bb = np.asarray(logical['rnn/%d/gates/bias' % l])
@@ -410,9 +414,10 @@ class ParamLayout:
                 Wx[:I, 2 * Hp:2 * Hp + H] = Kc[:I]
                 v('rnn%d/Wch' % l)[:H, :H] = Kc[I:]
                 rb[2 * Hp:2 * Hp + H] = bc
-            Wx[:I, :H] = K[:I, :H]; Wx[:I, Hp:Hp + H] = K[:I, H:]
-            Wh[:H, :H] = K[I:, :H]; Wh[:H, Hp:Hp + H] = K[I:, H:]
-            rb[:H] = bb[:H]; rb[Hp:Hp + H] = bb[H:]
+            for k in range(K.shape[1] // H):      # the column blocks of the one kernel (UGRNN g | c, GRU r | u, LSTM i | j | f | o), each padded to Hp
+                Wx[:I, k * Hp:k * Hp + H] = K[:I, k * H:(k + 1) * H]
+                Wh[:H, k * Hp:k * Hp + H] = K[I:, k * H:(k + 1) * H]
+                rb[k * Hp:k * Hp + H] = bb[k * H:(k + 1) * H]
         v('Wf1')[:H] = logical['FC1/kernel']; v('bf1')[...] = logical['FC1/bias']
         v('Wf2')[...] = logical['FC2/kernel']; v('bf2')[...] = logical['FC2/bias']
         for i, (w, bn) in enumerate([('Ws1', 'bs1'), ('Ws2', 'bs2'), ('Ws3', 'bs3')]):
@@ -438,14 +443,16 @@ class ParamLayout:
         for l in range(self.L):
             I = C if l == 0 else H
             Wx, Wh, rb = v('rnn%d/Wx' % l), v('rnn%d/Wh' % l), v('rnn%d/b' % l)
-            top = np.concatenate([Wx[:I, :H], Wx[:I, Hp:Hp + H]], 1)
-            bot = np.concatenate([Wh[:H, :H], Wh[:H, Hp:Hp + H]], 1)
-            if self.cell == 'ugrnn':
+            nb = Wh.shape[1] // Hp                # column blocks of the one kernel, see pack()
+            top = np.concatenate([Wx[:I, k * Hp:k * Hp + H] for k in range(nb)], 1)
+            bot = np.concatenate([Wh[:H, k * Hp:k * Hp + H] for k in range(nb)], 1)
+            bias = np.concatenate([rb[k * Hp:k * Hp + H] for k in range(nb)])
+            if self.cell in ('ugrnn', 'lstm'):
                 out['rnn/%d/kernel' % l] = np.concatenate([top, bot], 0)
-                out['rnn/%d/bias' % l] = np.concatenate([rb[:H], rb[Hp:Hp + H]])
+                out['rnn/%d/bias' % l] = bias
             else:
                 out['rnn/%d/gates/kernel' % l] = np.concatenate([top, bot], 0)
-                out['rnn/%d/gates/bias' % l] = np.concatenate([rb[:H], rb[Hp:Hp + H]])
+                out['rnn/%d/gates/bias' % l] = bias
                 out['rnn/%d/candidate/kernel' % l] = np.concatenate([Wx[:I, 2 * Hp:2 * Hp + H], v('rnn%d/Wch' % l)[:H, :H]], 0)
                 out['rnn/%d/candidate/bias' % l] = rb[2 * Hp:2 * Hp + H].copy()
         out['FC1/kernel'] = v('Wf1')[:H].copy(); out['FC1/bias'] = v('bf1').copy()

@@ -676,9 +676,9 @@ class StepPlan:
         self.hprev = [f32(BT, Hp) for _ in range(L.L)]
         self.G = [f32(BT, Hp) for _ in range(L.L)]
         self.Cc = [f32(BT, Hp) for _ in range(L.L)]
-        gru = L.cell == 'gru'
-        self.R = [f32(BT, Hp) if gru else None for _ in range(L.L)]
-        self.RH = [f32(BT, Hp) if gru else None for _ in range(L.L)]
+        four = L.cell in ('gru', 'lstm')          # GRU: r and r * h_prev; LSTM: its third and fourth gate
+        self.R = [f32(BT, Hp) if four else None for _ in range(L.L)]
+        self.RH = [f32(BT, Hp) if four else None for _ in range(L.L)]
         self.drnn = f32(BT, Hp)
         # FCs / scorer
         self.FC1, self.dFC1 = f32(BT, 512), f32(BT, 512)

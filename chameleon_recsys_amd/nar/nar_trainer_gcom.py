@@ -85,9 +85,10 @@ def define_flags():
     a('--use_local_cache_model_dir', type=_bool, default=False, nargs='?', const=True)
     a('--job-dir', default='./tmp')
     # ---- extensions of this implementation (not in the reference's flag set)
-    a('--rnn_cell', default='ugrnn', choices=['ugrnn', 'gru'], help="recurrent cell: 'ugrnn' = the reference's tf.contrib.rnn.UGRNNCell "
-      "(nar_model.py:1317), 'gru' = its commented-out GRUCell alternative (:1315).  Both take --rnn_units up to 1024: the fused time-loop "
-      "kernels up to 512 (ugrnn) / 384 (gru), one launch sequence per time step beyond")
+    a('--rnn_cell', default='ugrnn', choices=['ugrnn', 'gru', 'lstm'], help="recurrent cell: 'ugrnn' = the reference's tf.contrib.rnn.UGRNNCell "
+      "(nar_model.py:1317), 'gru' / 'lstm' = its commented-out GRUCell and LSTMCell alternatives (:1315-1316).  All take --rnn_units up to "
+      "1024: the fused time-loop kernels up to 512 (ugrnn) / 384 (gru), one launch sequence per time step beyond - and for the lstm at "
+      "every width")
     a('--gemm_dtype', default='f32', choices=['f32', 'f32_native', 'bf16'],
       help="f32: fp32 operands and fp32-grade error, wide GEMMs as six bf16-plane products on the bf16 matrix cores (caveats: an INFINITE "
            "operand yields NaN where fp32 yields +-inf - behind a tanh layer the native path saturates to a finite +-1 instead - and "

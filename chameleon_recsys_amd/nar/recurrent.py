@@ -5,12 +5,14 @@
 #   CoopUgrnn       UGRNN at Hp 256 on eight cooperating workgroups per 32 sessions (csrc/rnn_coop.hip), steps of few candidate rows
 #   StepwiseUgrnn   widths beyond LDS: per time step 1 GEMM + 1 point-wise kernel forward, 1 kernel + copy + accumulating GEMM backward
 #   StepwiseGru     ... 2 GEMMs + 2 kernels forward, 2 kernels + 2 GEMMs + 1 copy backward (the candidate needs r * h of ALL hidden units)
+#   StepwiseLstm    the LSTM at every width: the UGRNN's launches over four gate blocks; the cell state c lives in the point kernels
 # path_class() is the one place that chooses; the driver stores the path on the plan (pl.rnn), as it does pl.arm, and backward() reads it: a
 # backward that chose differently would read planes its forward never wrote.
 # A path is handed a HOST and uses nothing else of it: host.lib, host.gemm(A, B, C, M, N, K, lda, ldb, ldc, transB=, accumulate=, force_f32=),
 # the weight lookup host.p(name) - and, in wgrads() only, host.g(name) and host.colsum() - so scripts/bench_rnn_stepwise.py drives these classes
 # without a model.  (host.lib is read per call: tools replace it on a live runtime.)  Buffers: the plan keeps what every path reads and
-# writes (seq_len, xproj, dxproj, rnn_out, hprev, G, Cc, R, RH, drnn - the driver and the weight gradients read them too); alloc() adds what
+# writes (seq_len, xproj, dxproj, rnn_out, hprev, G, Cc, R, RH, drnn - the driver and the weight gradients read them too; the LSTM keeps its
+# gates i, j, f, o in G, Cc, R, RH); alloc() adds what
 # only this path needs, under the names below.  A new path subclasses the nearest one, implements alloc / forward / backward for one layer
 # `l` on the current stream (`s`: its raw handle), leaves rnn_out / hprev / G / Cc (GRU: + R, RH) and dxproj as the others do - wgrads() and
 # the driver read them - and gets its line in path_class().
@@ -31,7 +33,7 @@ def default_coop_rows(L):
 def path_class(L, PC, B, coop_rows):
     """The path of a step with PC candidate rows over B sessions (L: the ParamLayout, coop_rows: NARRuntime.rnn_coop_rows at this moment)."""
     if L.rnn_stepwise:
-        return StepwiseGru if L.cell == 'gru' else StepwiseUgrnn
+        return {'gru': StepwiseGru, 'lstm': StepwiseLstm}.get(L.cell, StepwiseUgrnn)
     return CoopUgrnn if (0 < PC <= coop_rows and B <= 1024) else FusedRnn
 
 
@@ -41,10 +43,11 @@ class RnnPath:
 
     def __init__(self, host, L):
         self.host, self.Hp, self.NGH, self.cell = host, L.Hp, L.NG * L.Hp, (1 if L.cell == 'gru' else 0)
+        self.WhN = (4 if L.cell == 'lstm' else 2) * L.Hp      # columns of W_h, the recurrent gate product (GRU: r | u; its candidate has W_ch)
 
     def wgrads(self, pl, l):      # recurrent weights: their forward product runs in the fp32 time-step kernel -> fp32 wgrad in every mode
-        h, Hp, NGH, BTf = self.host, self.Hp, self.NGH, pl.BT
-        h.gemm(pl.hprev[l], pl.dxproj, h.g('rnn%d/Wh' % l), Hp, 2 * Hp, BTf, Hp, NGH, 2 * Hp, transA=1, splits=0, force_f32=True)
+        h, Hp, NGH, WhN, BTf = self.host, self.Hp, self.NGH, self.WhN, pl.BT
+        h.gemm(pl.hprev[l], pl.dxproj, h.g('rnn%d/Wh' % l), Hp, WhN, BTf, Hp, NGH, WhN, transA=1, splits=0, force_f32=True)
         if self.cell == 1:   # candidate kernel: (r * h_prev)^T dz_c
             h.gemm(pl.RH[l], pl.dxproj[:, 2 * Hp:], h.g('rnn%d/Wch' % l), Hp, Hp, BTf, Hp, NGH, Hp, transA=1, splits=0, force_f32=True)
         h.colsum(pl.dxproj, NGH, BTf, NGH, h.g('rnn%d/b' % l))
@@ -107,24 +110,30 @@ class StepwiseUgrnn(RnnPath):
 
     def alloc(self, pl, f32):      # the running state, its gate product, and the backward's state gradient with its two summands
         B, Hp = pl.B, self.Hp
-        pl.h_state, pl.zh, pl.carry = f32(B, Hp), f32(B, 2 * Hp), f32(B, Hp)
-        pl.dzs, pl.direct = f32(B, 2 * Hp), f32(B, Hp)
+        pl.h_state, pl.zh, pl.carry = f32(B, Hp), f32(B, self.WhN), f32(B, Hp)
+        pl.dzs, pl.direct = f32(B, self.WhN), f32(B, Hp)
 
     def forward(self, pl, l, s):
-        Hp, Wh = self.Hp, self.host.p('rnn%d/Wh' % l)
-        pl.h_state.zero_()
+        Hp, WhN, Wh = self.Hp, self.WhN, self.host.p('rnn%d/Wh' % l)
+        self.zero_state(pl)
         for t in range(pl.T):
-            self.host.gemm(pl.h_state, Wh, pl.zh, pl.B, 2 * Hp, Hp, Hp, 2 * Hp, 2 * Hp, force_f32=True)      # zh = h W_h (GRU: the r | u columns, W_gh)
+            self.host.gemm(pl.h_state, Wh, pl.zh, pl.B, WhN, Hp, Hp, WhN, WhN, force_f32=True)      # zh = h W_h (GRU: the r | u columns, W_gh)
             self.point_fwd(pl, l, t, s)
 
     def backward(self, pl, l, s):
-        Hp, Wh = self.Hp, self.host.p('rnn%d/Wh' % l)
-        pl.carry.zero_()
+        Hp, WhN, Wh = self.Hp, self.WhN, self.host.p('rnn%d/Wh' % l)
+        self.zero_carry(pl)
         for t in range(pl.T - 1, -1, -1):
             self.point_bwd(pl, l, t, s)
             # carry = direct + dzs W_h^T, GRU: [dz_r | dz_u] W_gh^T  (rows beyond their length: dzs = 0, direct = carry -> unchanged)
             pl.carry.copy_(pl.direct)
-            self.host.gemm(pl.dzs, Wh, pl.carry, pl.B, Hp, 2 * Hp, 2 * Hp, 2 * Hp, Hp, transB=1, accumulate=1, force_f32=True)
+            self.host.gemm(pl.dzs, Wh, pl.carry, pl.B, Hp, WhN, WhN, WhN, Hp, transB=1, accumulate=1, force_f32=True)
+
+    def zero_state(self, pl):      # a layer's forward starts from the zero state, its backward from a zero state gradient
+        pl.h_state.zero_()
+
+    def zero_carry(self, pl):
+        pl.carry.zero_()
 
     def point_fwd(self, pl, l, t, s):
         check(self.host.lib.cham_ugrnn_point_fwd(ptr(pl.xproj[l]), ptr(pl.zh), ptr(pl.seq_len), pl.B, pl.T, t, self.Hp, ptr(pl.h_state), ptr(pl.rnn_out[l]),
@@ -158,3 +167,33 @@ class StepwiseGru(StepwiseUgrnn):
         self.host.gemm(pl.dzc, self.host.p('rnn%d/Wch' % l), pl.drh, B, Hp, Hp, Hp, Hp, Hp, transB=1, force_f32=True)     # d(r h) = dzc W_ch^T
         check(lib.cham_gru_point_r_bwd(ptr(pl.drh), ptr(pl.seq_len), B, T, t, Hp, ptr(pl.hprev[l]), ptr(pl.R[l]), ptr(pl.dxproj), ptr(pl.dzs),
                                        ptr(pl.direct), s), "cham_gru_point_r_bwd")
+
+
+class StepwiseLstm(StepwiseUgrnn):
+    """LSTM, step-wise at every width: the UGRNN's time loops over four gate blocks i | j | f | o; c and its gradient never leave the kernels."""
+    # the gates share the plan's planes with the other cells' (G = i, Cc = j, R = f, RH = o); hprev is, as everywhere, the Wh gradient's operand
+    launches_per_step = (2, 3)
+
+    def alloc(self, pl, f32):      # + the second state and its gradient, and per layer the two planes the plan has no name for: c_{t-1}, tanh(c_t)
+        StepwiseUgrnn.alloc(self, pl, f32)
+        pl.c_state, pl.carry_c = f32(pl.B, self.Hp), f32(pl.B, self.Hp)
+        pl.cprev = [f32(pl.B * pl.T, self.Hp) for _ in pl.hprev]
+        pl.TC = [f32(pl.B * pl.T, self.Hp) for _ in pl.hprev]
+
+    def zero_state(self, pl):
+        pl.h_state.zero_()
+        pl.c_state.zero_()
+
+    def zero_carry(self, pl):
+        pl.carry.zero_()
+        pl.carry_c.zero_()
+
+    def point_fwd(self, pl, l, t, s):
+        check(self.host.lib.cham_lstm_point_fwd(ptr(pl.xproj[l]), ptr(pl.zh), ptr(pl.seq_len), pl.B, pl.T, t, self.Hp, ptr(pl.h_state), ptr(pl.c_state),
+                                                ptr(pl.rnn_out[l]), ptr(pl.hprev[l]), ptr(pl.cprev[l]), ptr(pl.G[l]), ptr(pl.Cc[l]), ptr(pl.R[l]),
+                                                ptr(pl.RH[l]), ptr(pl.TC[l]), s), "cham_lstm_point_fwd")
+
+    def point_bwd(self, pl, l, t, s):
+        check(self.host.lib.cham_lstm_point_bwd(ptr(pl.drnn), ptr(pl.carry), ptr(pl.carry_c), ptr(pl.seq_len), pl.B, pl.T, t, self.Hp, ptr(pl.cprev[l]),
+                                                ptr(pl.G[l]), ptr(pl.Cc[l]), ptr(pl.R[l]), ptr(pl.RH[l]), ptr(pl.TC[l]), ptr(pl.dxproj), ptr(pl.dzs),
+                                                ptr(pl.direct), s), "cham_lstm_point_bwd")

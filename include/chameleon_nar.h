@@ -444,6 +444,23 @@ int cham_gru_point_c_bwd(const float* dout, const float* carry, const int32_t* s
                          void* stream);
 int cham_gru_point_r_bwd(const float* drh, const int32_t* seq_len, int B, int T, int t, int Hp, const float* hprev, const float* R,
                          float* dxproj, float* dzs, float* direct, void* stream);
+/* the LSTM (tf.nn.rnn_cell.LSTMCell, the third cell named at nar_model.py:1315-1317; TF 1.12 defaults: no peepholes, projection or
+ * clipping, forget_bias 1), step-wise at every width: xproj / zh / dxproj / dzs hold 4Hp columns in TF's block order i | j | f | o,
+ * W_h is [Hp,4Hp], planes are [B,T,Hp].  One recurrent GEMM and one kernel per step and direction, as for the UGRNN:
+ *   forward   zh [B,4Hp] = h W_h;  point_fwd: i = s(z_i), j = tanh(z_j), f = s(z_f + 1), o = s(z_o) with z = zh + xproj[:,t];
+ *             c' = f c + i j, h' = o tanh(c');  writes hprev[:,t] = h, cprev[:,t] = c, Gi, Gj, Gf, Go, TC (= tanh(c')),
+ *             out[:,t] = t < len ? h' : 0;  h = h' and c = c' where t < len (both states [B,Hp], in place)
+ *   backward  (t descending, carry_h and carry_c [B,Hp] starting at 0)  point_bwd: dh = dout[:,t] + carry_h, dc = carry_c + dh o (1 - TC^2);
+ *             dz_i = dc j i(1-i), dz_j = dc i (1-j^2), dz_f = dc cprev f(1-f), dz_o = dh TC o(1-o) to dxproj[:,t] and dzs [B,4Hp];
+ *             carry_c = dc f in place, direct = 0 (beyond the length: dz = 0, direct = carry_h, carry_c unchanged);
+ *             carry_h = direct + dzs W_h^T
+ * Every plane is written at every t, also beyond a session's length; rows >= B are not touched; plain stores (two runs are
+ * bit-identical).  NULL pointers or t outside [0, T): -EINVAL, nothing launched. */
+int cham_lstm_point_fwd(const float* xproj, const float* zh, const int32_t* seq_len, int B, int T, int t, int Hp, float* h, float* c,
+                        float* out, float* hprev, float* cprev, float* Gi, float* Gj, float* Gf, float* Go, float* TC, void* stream);
+int cham_lstm_point_bwd(const float* dout, const float* carry_h, float* carry_c, const int32_t* seq_len, int B, int T, int t, int Hp,
+                        const float* cprev, const float* Gi, const float* Gj, const float* Gf, const float* Go, const float* TC,
+                        float* dxproj, float* dzs, float* direct, void* stream);
 int cham_transpose_f32(const float* in, int rows, int cols, float* out, void* stream);
 /* valid-position compaction (the mask of nar_model.py:231 applied as a row selection instead of a multiply): rows are
  * `words` 32-bit words wide; gather: dst[i] = src[pos[i]], scatter: dst[pos[i]] = src[i] (other rows of dst untouched) */

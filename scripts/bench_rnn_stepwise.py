@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Time of the recurrent stack alone, forward + backward of one layer, through the model's own launch paths (nar/recurrent.py): the
-step-wise GRU (rnn_units above 384) next to the step-wise UGRNN and the fused GRU.  Full-length sessions; the x W_x projection and the
+step-wise GRU (rnn_units above 384) and the step-wise LSTM (every width) next to the step-wise UGRNN and the fused GRU.  Full-length sessions; the x W_x projection and the
 weight gradients are not part of it (they are the same GEMMs for every path).
 
   python scripts/bench_rnn_stepwise.py [--batch 256] [--seq 20] [--warmup 5] [--iters 20] [--rounds 3] [--out FILE]
@@ -26,7 +26,7 @@ from chameleon_recsys_amd._lib import check, ptr         # noqa: E402
 from chameleon_recsys_amd.nar import recurrent            # noqa: E402
 from chameleon_recsys_amd.nar.layout import rnn_stepwise  # noqa: E402
 
-CASES = [('gru', 512), ('gru', 1024), ('ugrnn', 640), ('ugrnn', 1024), ('gru', 384)]
+CASES = [('gru', 512), ('gru', 1024), ('ugrnn', 640), ('ugrnn', 1024), ('gru', 384), ('lstm', 256), ('lstm', 512), ('lstm', 640), ('lstm', 1024)]
 
 
 class Stack:
@@ -35,21 +35,22 @@ class Stack:
 
     def __init__(self, lib, cell, Hp, B, T, dev, seed=0):
         self.lib, self.cell, self.Hp, self.B, self.T, self.BT = lib, cell, Hp, B, T, B * T
-        gru = cell == 'gru'
-        ng = 3 if gru else 2
+        gru, four = cell == 'gru', cell in ('gru', 'lstm')
+        ng = {'ugrnn': 2, 'gru': 3, 'lstm': 4}[cell]
+        nh = 4 if cell == 'lstm' else 2      # column blocks of W_h
         L = types.SimpleNamespace(cell=cell, Hp=Hp, NG=ng, rnn_stepwise=rnn_stepwise(cell, Hp))
         g = torch.Generator(device=dev)
         g.manual_seed(seed + Hp)
         rnd = lambda *s: torch.randn(*s, generator=g, device=dev, dtype=torch.float32)
         f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
-        # W_gh [Hp, 2Hp] directly followed by W_ch [Hp, Hp], as the flat parameter buffer holds them
+        # W_gh [Hp, 2Hp] directly followed by W_ch [Hp, Hp], as the flat parameter buffer holds them (LSTM: one W_h [Hp, 4Hp])
         W = rnd(Hp * ng * Hp) * Hp ** -0.5
-        self.weights = {'rnn0/Wh': W[:2 * Hp * Hp].view(Hp, 2 * Hp), 'rnn0/Wch': W[2 * Hp * Hp:].view(Hp, Hp) if gru else None}
+        self.weights = {'rnn0/Wh': W[:nh * Hp * Hp].view(Hp, nh * Hp), 'rnn0/Wch': W[2 * Hp * Hp:].view(Hp, Hp) if gru else None}
         self.p = self.weights.__getitem__
         self.xproj, self.drnn = [0.7 * rnd(B * T, ng * Hp)], rnd(B * T, Hp)
         self.seq_len = torch.full((B,), T, dtype=torch.int32, device=dev)
         self.rnn_out, self.hprev, self.G, self.Cc = ([f32(B * T, Hp)] for _ in range(4))
-        self.R, self.RH = ([f32(B * T, Hp) if gru else None] for _ in range(2))
+        self.R, self.RH = ([f32(B * T, Hp) if four else None] for _ in range(2))
         self.dxproj = f32(B * T, ng * Hp)
         # (PC 0: a step without candidate rows - never the cooperative path, which is not a case here)
         self.path = recurrent.path_class(L, 0, B, recurrent.default_coop_rows(L))(self, L)

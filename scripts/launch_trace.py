@@ -49,6 +49,8 @@ CONFIGS = {
     'gru_wide': ({}, {'rnn_cell': 'gru', 'H': 500}, {}, 'g1', 0),                          # Hp 512: step-wise GRU
     'gru_wide2': ({}, {'rnn_cell': 'gru', 'H': 400, 'rnn_num_layers': 2}, {}, 'g1', 0),
     'gru_dropout': ({}, {'rnn_cell': 'gru', 'H': 500, 'dropout_keep_prob': 0.8}, {}, 'g1', 0),
+    'lstm': ({}, {'rnn_cell': 'lstm'}, {}, 'g1', 0),                                       # step-wise at every width
+    'lstm2': ({}, {'rnn_cell': 'lstm', 'H': 400, 'rnn_num_layers': 2}, {}, 'g1', 0),
     'full_length': ({}, {}, {}, 'full', 0),
     'microbatched': ({}, {}, {}, 'g1', 8),
 }
