@@ -74,10 +74,10 @@ class F32Rows:
                                                          rowscale=False, dmf=True, tile=0, epi=0, **flags))
 
     # ---- forward
-    def z1(self, pl, s, drop):      # candidate rows of the PreCAR output; drop = the step's dropout record (dense rows x the stacked W1) or None (U + V)
+    def z1(self, pl, s, drop):      # candidate rows of the PreCAR output; drop = the step's dense input form (nar/input_rows.py: dense rows x the stacked W1) or None (U + V)
         rt, C, P, R = self.rt, pl.C, pl.P, pl.PC
         if drop:
-            rt.gemm(pl.Xd[P:], drop['W1'], pl.Z1[P:], R, C, drop['Fw'], drop['Fw'], C, C, bias=rt.p('b1'), act=ACT_LEAKY)
+            rt.gemm(pl.Xd[P:], drop.W1, pl.Z1[P:], R, C, drop.Fw, drop.Fw, C, C, bias=rt.p('b1'), act=ACT_LEAKY)
         else:
             check(rt.lib.cham_combine_fwd(ptr(pl.U), ptr(pl.V), C, P, pl.N, pl.pmax, ptr(pl.cur_neg_slot), ptr(pl.Z1), P, R, s), "cham_combine_fwd")
 
@@ -363,7 +363,7 @@ class Bf16Rows(F32Rows):
     def z1(self, pl, s, drop):
         rt, C, P, R = self.rt, pl.C, pl.P, pl.PC
         if drop:      # dense PreCAR rows (masks differ per occurrence): bf16-rounded operands, fp32 out, stored as the bf16-resident Z1c
-            rt.gemm(pl.Xd[P:], drop['W1'], pl.Z1f[P:], R, C, drop['Fw'], drop['Fw'], C, C, bias=rt.p('b1'), act=ACT_LEAKY)
+            rt.gemm(pl.Xd[P:], drop.W1, pl.Z1f[P:], R, C, drop.Fw, drop.Fw, C, C, bias=rt.p('b1'), act=ACT_LEAKY)
             check(rt.lib.cham_cast_b16(pl.Z1f[P:].data_ptr(), R, C, ptr(pl.Z1c), None, s), "cham_cast_b16")
         else:
             check(rt.lib.cham_combine_fwd_b16(ptr(pl.U), ptr(pl.V), C, P, pl.N, pl.pmax, ptr(pl.cur_neg_slot), ptr(pl.Z1c), s), "cham_combine_fwd_b16")

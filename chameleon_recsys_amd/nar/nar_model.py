@@ -24,7 +24,8 @@ from .candidate_rows import (ACT_LEAKY, ACT_NONE, ACT_TANH, Bf16Rows, F32Rows, H
                              planes_from_blocked, planes_to_blocked)
 from . import recurrent
 from .clicked_items_state import lane_stream
-from .layout import COL_ITEMEMB, ParamLayout
+from .input_rows import SITE_FC1, SITE_RNN_OUT, DenseInput, Dropout, FactorisedInput, FeatureRows, step_scalar
+from .layout import ParamLayout
 from .metrics import BEYOND_ACCURACY_PER_CLICK, ItemCoverage
 
 
@@ -158,6 +159,7 @@ class NARRuntime:
     resident article tables (ACE matrix, metadata - re-fed from numpy every step by the reference,
     nar_model.py:1458-1467), global step, workspaces."""
     plans_created = 0         # plans built by plan() (bookkeeping: a first-seen padded length costs GBs of allocation)
+    stream = staticmethod(_stream)      # raw handle of torch's current stream: what the arithmetic modules launch on
 
     def __init__(self, params, device='cuda:0', seed=42, weights=None):
         self.lib = _lib.load()
@@ -243,34 +245,10 @@ class NARRuntime:
         self.dm_f16 = self.s1_h2                  # the fused dgrad's own products
         self.s1_h2_fwd = mode == "a"              # the forward GEMM
         self.tf_random_seed = int(params.get('tf_random_seed', 42))
-        # resident article tables
-        meta = params['articles_metadata']
-        self.ace = torch.from_numpy(ace).to(dev)
-        self.created = torch.from_numpy(np.ascontiguousarray(meta['created_at_ts'], dtype=np.int64)).to(dev)
-        def meta_column(n):
-            # metadata columns live in ONE int64 table.  A float-valued numerical article feature (config dtype 'float',
-            # nar_model.py:755-757) is stored as its float32 bit pattern and read back bit-exactly by the assemble kernels
-            # (layout.meta_is_float -> descriptor sub-field 1); everything else as the integer it is.
-            a = np.asarray(meta[n])
-            if n in L.meta_is_float:
-                return np.ascontiguousarray(a, dtype=np.float32).view(np.int32).astype(np.int64)
-            if acfg[n]['type'] == 'numerical' and not np.issubdtype(a.dtype, np.integer) and not np.array_equal(a, np.round(a)):
-                raise ValueError("article feature %r holds non-integer values but its config says dtype %r: declare it "
-                                 "{'type': 'numerical', 'dtype': 'float'}" % (n, acfg[n].get('dtype')))
-            return a.astype(np.int64)
-        if L.meta_names:
-            mc = np.stack([meta_column(n) for n in L.meta_names])
-        else:
-            mc = np.zeros((1, self.n_items), np.int64)
-        self.meta_cat = torch.from_numpy(np.ascontiguousarray(mc)).to(dev)
-        self.ctx_desc = torch.from_numpy(L.ctx_descriptors()).to(dev)
-        self.ctx_emb_groups, self.item_emb_groups = L.ctx_emb_groups(), L.item_emb_groups()
-        segs, singles = L.item_segments()
-        self.item_segs, self.n_item_segs = torch.from_numpy(np.ascontiguousarray(segs)).to(dev), int(segs.shape[0])
-        self.item_singles, self.n_item_singles = torch.from_numpy(np.ascontiguousarray(singles)).to(dev), int(singles.shape[0])
-        # item rows through LDS tiles (csrc/features.hip k_item_assemble_lds); rows too wide for the tile: one thread per element
-        self.item_lds = L.Fi * 4 * 8 <= 64 * 1024
-        self.item_desc = torch.from_numpy(L.item_descriptors()).to(dev)
+        # The input rows (nar/input_rows.py): the feature front end - it puts the resident article tables and the feature descriptors here, as
+        # attributes of this runtime - and the factorised PreCAR input layer (the dense form of a step with dropout is built by that step)
+        self.features = FeatureRows(self, ace)
+        self.precar = FactorisedInput(self)
         self.gemm_ws = torch.empty(64 << 20, dtype=torch.float32, device=dev)        # 256 MB split-K partials (main stream)
         self.colsum_ws = torch.empty(4 << 20, dtype=torch.float32, device=dev)
         # the recurrent branch (8 CUs busy) runs on a side stream, overlapped with the candidate-row CAR GEMMs (normal priority: a
@@ -658,9 +636,8 @@ class StepPlan:
         self.group_ws = torch.zeros(int(rt.lib.cham_group_rows_workspace_bytes(RV)) // 4, dtype=torch.int32, device=dev)
         self.Xc_raw, self.Xc_s, self.dXc = f32(BT, Fc), f32(BT, Fc), f32(BT, Fc)
         self.Xi_raw, self.Xi_s, self.dXi = f32(RV, Fi), f32(RV, Fi), f32(RV, Fi)
-        # CAR
-        self.U, self.dU = f32(BT, C), f32(BT, C)
-        self.V, self.dV = f32(RV, C), f32(RV, C)
+        # PreCAR input layer (nar/input_rows.py: the factorised form; the dense form of the dropout path allocates on its first step), CAR
+        rt.precar.alloc(self, f32)
         # Z1, Z2, dZ2, dZ1 (+ planes, scale records, b2 partial sums) in the arithmetic the plan is built for; self.arm: the arm of the LAST
         # step on this plan (forward() sets it, backward() and cand_Z1() read it)
         self.gsum = self.arm = None
@@ -703,8 +680,9 @@ class StepPlan:
         self.rnn = rt.rnn_path(self)
         self.rnn.alloc(self, f32)
         # made on first need: the event of the side lane's row grouping (training-mode forward), the item rows a data-parallel step can touch
-        # (sparse modes), dropout_buffers(); nbytes: set by NARRuntime.plan once the plan is built
-        self.grouped_ev = self.touched = self.Xd = None
+        # (sparse modes), the dense input form's buffers; precar: the input form of the LAST step on this plan, cat: its context columns
+        # (nar/input_rows.py); nbytes: set by NARRuntime.plan once the plan is built
+        self.grouped_ev = self.touched = self.Xd = self.precar = self.cat = None
         self.nbytes = 0
         # The zero fills above run on the stream that built the plan.  A stream that touches these buffers without being ordered behind
         # that point must wait for this event first: presample() may be the FIRST user of a plan (a padded length T seen for the first
@@ -721,23 +699,6 @@ class StepPlan:
             setattr(self, name, t)
             self.nbytes = self.allocated_bytes()         # what the plan cache's byte budget counts (NARRuntime.plan)
         return t
-
-    def dropout_buffers(self, rt):
-        """Buffers of the dropout path (keep_prob < 1: dense PreCAR input rows, dropped FC1 / recurrent outputs) - allocated on first use."""
-        if not rt.b16:
-            self.ensure_rows('Z1'); self.ensure_rows('dZ2')
-        if self.Xd is None:
-            L, dev = rt.layout, rt.device
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-            Fw = L.Fc + L.Fi
-            self.Xd, self.dXd = f32(self.Rall, Fw), f32(self.Rall, Fw)
-            self.dUx, self.dVx = f32(self.BT, Fw), f32(self.RV, Fw)
-            self.FC1d = f32(self.BT, 512)
-            self.rnn_drop = [f32(self.BT, L.Hp) for _ in range(L.L)]
-            need = rt.lib.cham_combine_bwd_workspace_bytes(Fw, self.B * self.T, self.N, self.pmax)
-            self.drop_ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
-            if rt.b16:      # bf16 configuration: the dense PreCAR layer computes / consumes fp32 images of the bf16-resident candidate rows
-                self.Z1f, self.dZ1f = f32(self.Rall, L.C), f32(self.Rall, L.C)
 
     def cand_Z1(self, P=None):
         """Candidate rows of the PreCAR output of the last step as fp32 [P * NC, C] (tests): the fp32 matrix, or the sum of its planes."""
@@ -1037,9 +998,9 @@ class NARModuleModel:
                 shadows_ev.record()
         # BT = rows of the row-wise stages = the P valid positions (all B*T when nothing is padded); BTf = the [B, T] layout
         pos, BT, BTf, NC, pmax = d['pos'], d['P'], pl.BT, pl.NC, pl.pmax
-        Rc = BT * NC; RV = 2 * BT + pmax + 1
+        Rc = BT * NC
         pl.pos, pl.P, pl.PC = pos, BT, Rc
-        C, Hp, Fc, Fi = L.C, L.Hp, L.Fc, L.Fi
+        C, Hp = L.C, L.Hp
         NGH = L.NG * L.Hp
         if step is None:
             step = rt.global_step if self.is_training else self.eval_step_key(rt.global_step, self._eval_iter)
@@ -1079,12 +1040,8 @@ class NARModuleModel:
         # K1 item row set = [clicked ; positives ; pool slots ; pad item 0]
         _roctx.pop(); _roctx.push("K1 features (gather, normalise, scale / center)")
         # (one launch - round 5: eight copy / fill launches before - also seq_len and the position mask of the stages below)
-        if dsc:
-            check(lib.cham_step_ints_dev(ptr(d['ic_rows']), ptr(d['ln_rows']), ptr(pl.pool), ptr(d['ets_rows']), ptr(rt.scalars), BT, pmax, ptr(d['seq_len']),
-                                         B, ptr(d['mask']), ptr(pl.ids_all), ptr(pl.ref_ts), ptr(pl.seq_len), ptr(pl.mask), s), "cham_step_ints_dev")
-        else:
-            check(lib.cham_step_ints(ptr(d['ic_rows']), ptr(d['ln_rows']), ptr(pl.pool), ptr(d['ets_rows']), int(d['max_ts']), BT, pmax, ptr(d['seq_len']),
-                                     B, ptr(d['mask']), ptr(pl.ids_all), ptr(pl.ref_ts), ptr(pl.seq_len), ptr(pl.mask), s), "cham_step_ints")
+        fr = rt.features
+        fr.step_ints(pl, d, s)
         pl.grouped_ev = None
         if self.is_training:      # rows of equal id made contiguous: the embedding-gradient sums of the backward pass (depends on ids only)
             if rt.overlap:        # ~10 launches nobody needs before the end of the backward: on the side lane, behind the id copies above
@@ -1092,47 +1049,14 @@ class NARModuleModel:
                 e_ids.record()
                 rt.side_stream.wait_event(e_ids)
                 with torch.cuda.stream(rt.side_stream):
-                    check(lib.cham_group_rows(ptr(pl.ids_all), RV, rt.item_id_bits, ptr(pl.perm), ptr(pl.seg), ptr(pl.group_ws),
-                                              pl.group_ws.numel() * 4, _stream()), "cham_group_rows")
+                    fr.group_rows(pl, _stream())
                     pl.grouped_ev = torch.cuda.Event()
                     pl.grouped_ev.record()
             else:
-                check(lib.cham_group_rows(ptr(pl.ids_all), RV, rt.item_id_bits, ptr(pl.perm), ptr(pl.seg), ptr(pl.group_ws),
-                                          pl.group_ws.numel() * 4, s), "cham_group_rows")
-        check(lib.cham_item_dynamic_raw(ptr(pl.ids_all), ptr(pl.ref_ts), RV, ptr(rt.created), ptr(st['pop_norm']),
-                                        ptr(pl.rec_raw), ptr(pl.nov_raw), s), "cham_item_dynamic_raw")
-        if st['n_last'] > 0 and st.get('device') and dsc:
-            check(lib.cham_norm_stats_from_buffer_dev(ptr(st['last']), st['n_last'], ptr(rt.scalars), ptr(rt.created),
-                                                      ptr(st['pop_norm']), ptr(pl.stat_scratch), ptr(pl.stats), s),
-                  "cham_norm_stats_from_buffer_dev")
-        elif st['n_last'] > 0 and st.get('device'):
-            check(lib.cham_norm_stats_from_buffer(ptr(st['last']), st['n_last'], d['max_ts'], ptr(rt.created),
-                                                  ptr(st['pop_norm']), ptr(pl.stat_scratch), ptr(pl.stats), s),
-                  "cham_norm_stats_from_buffer")
-        elif st['n_last'] > 0:
-            check(lib.cham_norm_stats_from_recent(ptr(st['last']), st['n_last'], d['max_ts'], ptr(rt.created),
-                                                  ptr(st['pop_norm']), ptr(pl.stat_scratch), ptr(pl.stats), s),
-                  "cham_norm_stats_from_recent")
-        else:   # very first batch: population = the call's own non-pad ids (nar_model.py:1078-1084)
-            check(lib.cham_row_weights(ptr(pl.ids_all), 2 * BT, ptr(neg_slot), BT * N, pmax, ptr(pl.pool),
-                                       ptr(pl.w_rows), pl.w_rows[2 * BT:].data_ptr(), s), "cham_row_weights")
-            for g, (a, b) in enumerate([(0, BT), (BT, 2 * BT), (2 * BT, RV)]):
-                check(lib.cham_norm_stats_from_rows(pl.rec_raw[a:].data_ptr(), pl.nov_raw[a:].data_ptr(),
-                                                    pl.w_rows[a:].data_ptr(), b - a, pl.stats[g].data_ptr(), s),
-                      "cham_norm_stats_from_rows")
-        check(lib.cham_ctx_assemble(ptr(d['cat']), ptr(d['num']), BT, ptr(rt.ctx_desc), Fc, ptr(rt.flat), ptr(p('gamma_ctx')),
-                                    ptr(p('beta_ctx')), ptr(pl.Xc_raw), ptr(pl.Xc_s), s), "cham_ctx_assemble")
-        if rt.item_lds:
-            check(lib.cham_item_assemble_lds(ptr(pl.ids_all), RV, BT, 2 * BT, ptr(rt.meta_cat), rt.n_items, ptr(rt.ace), L.D,
-                                             ptr(pl.rec_raw), ptr(pl.nov_raw), ptr(pl.stats), ptr(rt.item_desc), Fi, ptr(rt.item_segs),
-                                             rt.n_item_segs, ptr(rt.item_singles) if rt.n_item_singles else None, rt.n_item_singles,
-                                             ptr(rt.flat), ptr(p('gamma_item')), ptr(p('beta_item')), ptr(pl.Xi_raw), ptr(pl.Xi_s), s),
-                  "cham_item_assemble_lds")
-        else:
-            check(lib.cham_item_assemble(ptr(pl.ids_all), RV, BT, 2 * BT, ptr(rt.meta_cat), rt.n_items, ptr(rt.ace), L.D,
-                                         ptr(pl.rec_raw), ptr(pl.nov_raw), ptr(pl.stats), ptr(rt.item_desc), Fi, ptr(rt.flat),
-                                         ptr(p('gamma_item')), ptr(p('beta_item')), ptr(pl.Xi_raw), ptr(pl.Xi_s), s),
-                  "cham_item_assemble")
+                fr.group_rows(pl, s)
+        fr.dynamic_raw(pl, st, s)
+        fr.norm_stats(pl, d, st, s)
+        fr.assemble(pl, d, s)
         if shadows_ev is not None:
             torch.cuda.current_stream().wait_event(shadows_ev)
         else:
@@ -1142,39 +1066,19 @@ class NARModuleModel:
         # (full batches only: with ragged sessions the side lane's recurrent chain IS the critical path and the two launches are better
         # off on the main lane - G1-like lengths 114-115 k vs 111-112 k sessions/s, profiles/r05_notes.md)
         head_split = rt.head_split and rt.overlap and BT * NC > rt.w2_main_rows
-        if drop:
-            # dropout_keep_prob < 1 (nar_model.py:338, 352, 368): the per-element masks make every CAR row occurrence-specific, so
-            # the PreCAR layer runs on the dense [clicked | candidates] x [ctx | item] rows instead of the factorised U + V form
-            pl.dropout_buffers(rt)
-            keep, Fw, e1, e2 = float(self.keep_prob), Fc + Fi, L.entries['W1c'], L.entries['W1i']
-            assert e2.offset == e1.offset + e1.size
-            W1 = rt.flat[e1.offset:e2.offset + e2.size].view(Fw, C)
-            gW1 = rt.grads[e1.offset:e2.offset + e2.size].view(Fw, C)
-
-            def dropout(x, y, rows, cols, ld, site_first, site_rest, group, posmap, col_split=None, col_shift=0):
-                check(lib.cham_dropout(ptr(x), ptr(y), rows, cols, ld, keep, rt.tf_random_seed, step & 0xFFFFFFFF, site_first, site_rest,
-                                       group, ptr(posmap), T, d['row_begin'], cols if col_split is None else col_split, col_shift,
-                                       _stream()), "cham_dropout")
-            self._drop = dict(fn=dropout, W1=W1, gW1=gW1, Fw=Fw)
-            check(lib.cham_dense_rows(ptr(pl.Xc_s), Fc, ptr(pl.Xi_s), Fi, BT, N, pmax, ptr(neg_slot), ptr(pl.Xd), s), "cham_dense_rows")
-            dropout(pl.Xd, pl.Xd, BT, Fw, Fw, 16, 16, 1, pos, Fc, Fc - L.f_ctx)
-            dropout(pl.Xd[BT:], pl.Xd[BT:], Rc, Fw, Fw, 17, 18, NC, pos, Fc, Fc - L.f_ctx)
-            rt.gemm(pl.Xd, W1, pl.Z1, BT, C, Fw, Fw, C, C, bias=p('b1'), act=ACT_LEAKY)      # clicked-input rows first ...
-        else:
-            self._drop = None
-            # factorised PreCAR: U (per click) + V (per unique item row), then CAR
-            rt.gemm(pl.Xc_s, p('W1c'), pl.U, BT, C, Fc, Fc, C, C, bias=p('b1'))
-            rt.gemm(pl.Xi_s, p('W1i'), pl.V, RV, C, Fi, Fi, C, C)
-            # PreCAR combine + CAR layer 2 on the clicked-input rows first: they feed the recurrent branch ...
-            if not head_split:
-                check(lib.cham_combine_fwd(ptr(pl.U), ptr(pl.V), C, BT, N, pmax, ptr(neg_slot), ptr(pl.Z1), 0, BT, s), "cham_combine_fwd")
+        # the form of the PreCAR input layer (nar/input_rows.py), decided here, once: factorised U (per click) + V (per unique item row), or, with
+        # dropout, the dense rows under this step's masks - its forward() leaves the clicked-input rows' Z1 too
+        pre = pl.precar = DenseInput(rt, Dropout(rt, self.keep_prob, step, T, d['row_begin'])) if drop else rt.precar
+        dropout = pre.dropout
+        pre.forward(pl, s)
+        # PreCAR combine + CAR layer 2 on the clicked-input rows first: they feed the recurrent branch ...
         if not head_split:
+            pre.clicked_z1(pl, s)
             rt.gemm(pl.Z1, p('W2'), pl.Z2, BT, C, C, C, C, C, bias=p('b2'), act=ACT_TANH)
         rt.fork()
         with rt.side():   # ... which is latency-bound (one workgroup per 32 sessions) and overlaps with ...
             if head_split:      # (round 5) ... at the head of THIS lane: only the recurrent branch reads the clicked rows' CAR output
-                if not drop:
-                    check(lib.cham_combine_fwd(ptr(pl.U), ptr(pl.V), C, BT, N, pmax, ptr(neg_slot), ptr(pl.Z1), 0, BT, _stream()), "cham_combine_fwd")
+                pre.clicked_z1(pl, _stream())
                 rt.gemm(pl.Z1, p('W2'), pl.Z2, BT, C, C, C, C, C, bias=p('b2'), act=ACT_TANH)
             x, ldx, K = pl.Z2, C, C
             if pos is not None:          # clicked rows back into the [B, T] layout of the recurrent stack (zeros at padded steps)
@@ -1187,7 +1091,7 @@ class NARModuleModel:
                 rnn.forward(pl, l, _stream())
                 x, ldx, K = pl.rnn_out[l], Hp, Hp
                 if drop:     # DropoutWrapper(output_keep_prob), nar_model.py:1331: the layer's OUTPUT is dropped, its state is not
-                    dropout(pl.rnn_out[l], pl.rnn_drop[l], BTf, Hp, Hp, 20 + l, 20 + l, 1, None)
+                    dropout.apply(pl.rnn_out[l], pl.rnn_drop[l], BTf, Hp, Hp, SITE_RNN_OUT + l, SITE_RNN_OUT + l, 1, None)
                     x = pl.rnn_drop[l]
             if pos is not None:
                 check(lib.cham_rows_gather(ptr(x), ptr(pos), BT, Hp, ptr(pl.rnn_c), _stream()), "cham_rows_gather")
@@ -1195,13 +1099,13 @@ class NARModuleModel:
             rt.gemm(x, p('Wf1'), pl.FC1, BT, 512, Hp, Hp, 512, 512, bias=p('bf1'), act=ACT_LEAKY)
             fc1 = pl.FC1
             if drop:         # nar_model.py:418
-                dropout(pl.FC1, pl.FC1d, BT, 512, 512, 19, 19, 1, pos)
+                dropout.apply(pl.FC1, pl.FC1d, BT, 512, 512, SITE_FC1, SITE_FC1, 1, pos)
                 fc1 = pl.FC1d
             rt.gemm(fc1, p('Wf2'), pl.pred, BT, C, 512, 512, C, C, bias=p('bf2'), act=ACT_TANH)
         # ... the candidate rows: PreCAR combine (HBM-bound) + the dominant GEMM, CAR layer 2 on the B*T*(1+N) rows
         # in the arithmetic of this step (nar/candidate_rows.py), decided here, once: the configured arm, the fp32 rows where planes cannot be used
         arm = pl.arm = rt.step_arm(planes=not drop and Rc > 0)
-        arm.z1(pl, s, self._drop)
+        arm.z1(pl, s, pre if drop else None)
         arm.car_fwd(pl)
         rt.join()
         # scorer: (cand (.) pred) -> 128 -> 64 -> 32 -> 1, softmax(/tau), masked NLL
@@ -1212,12 +1116,8 @@ class NARModuleModel:
                                             ptr(neg_ids), ptr(st['pop_norm']), ptr(pl.nov_aux), s), "cham_score_softmax_fwd")
         def loss_kernels(s):
             check(lib.cham_sumsq_partial(ptr(rt.flat), L.n_reg, ptr(rt.sumsq), s), "cham_sumsq_partial")
-            if dsc:
-                check(lib.cham_loss_finalize_dev(ptr(pl.nll), BT, ptr(rt.scalars), ptr(rt.sumsq), float(self.reg_weight_decay), ptr(pl.loss), s),
-                      "cham_loss_finalize_dev")
-            else:
-                check(lib.cham_loss_finalize(ptr(pl.nll), BT, d['sum_mask'], ptr(rt.sumsq), float(self.reg_weight_decay), ptr(pl.loss), s),
-                      "cham_loss_finalize")
+            fn, sum_mask = step_scalar(rt, 'cham_loss_finalize', d['sum_mask'])      # (from the step-scalar record, or by value)
+            check(getattr(lib, fn)(ptr(pl.nll), BT, sum_mask, ptr(rt.sumsq), float(self.reg_weight_decay), ptr(pl.loss), s), fn)
         if getattr(self, '_defer_loss', False) and rt.overlap and rt.loss_side:
             # inside a training step (train_step: forward -> backward -> Adam) the L2 term and the loss record leave the main lane - nothing in
             # the backward pass reads them, they sat between the softmax and its backward (round 6); the backward's final join covers them
@@ -1246,16 +1146,17 @@ class NARModuleModel:
         # (different bases) may have run its forward pass since ours
         check(lib.cham_set_log_bases(self.elapsed_days_smooth_log_base, self.popularity_smooth_log_base), "cham_set_log_bases")
         s = _stream()
-        B, T, N = pl.B, pl.T, pl.N
-        pos, BT, BTf, NC, pmax = pl.pos, pl.P, pl.BT, pl.NC, pl.pmax          # see forward(): BT = valid positions
-        Rc = BT * NC; Rall = BT + Rc; RV = 2 * BT + pmax + 1
-        neg_ids, neg_slot = pl.cur_neg_ids, pl.cur_neg_slot
-        C, Hp, Fc, Fi = L.C, L.Hp, L.Fc, L.Fi
+        N = pl.N
+        pos, BT, BTf, NC = pl.pos, pl.P, pl.BT, pl.NC          # see forward(): BT = valid positions
+        Rc = BT * NC
+        neg_ids = pl.cur_neg_ids
+        C, Hp = L.C, L.Hp
         cell, NGH = (1 if L.cell == 'gru' else 0), L.NG * L.Hp
         p, g = rt.p, rt.g
         main_stream, on = torch.cuda.current_stream(), rt.overlap
-        drop = self._drop
-        dropout = drop['fn'] if drop else None
+        pre = pl.precar                  # the form of the PreCAR input layer, as forward() chose it (nar/input_rows.py) ...
+        dropout = pre.dropout            # ... and the step's masks, if it had any
+        drop = dropout is not None
         arm = pl.arm                     # the arithmetic of the candidate rows, as forward() chose it (nar/candidate_rows.py)
         b16 = arm.b16
 
@@ -1357,7 +1258,7 @@ class NARModuleModel:
                     rt.dp_early_bucket(rt.grads)     # data parallel: [Wf1 .. Ws4] gradients are final - their all-reduce starts now
             rt.gemm(pl.dpred, p('Wf2'), pl.dFC1, BT, 512, C, C, C, 512, transB=1, dref=pl.FC1, ldr=512, dact=ACT_LEAKY)
             if drop:                     # (mask and leaky' are both element-wise factors: the order does not matter)
-                dropout(pl.dFC1, pl.dFC1, BT, 512, 512, 19, 19, 1, pos)
+                dropout.apply(pl.dFC1, pl.dFC1, BT, 512, 512, SITE_FC1, SITE_FC1, 1, pos)
             if not crit_first:
                 fc_wgrads()
             if pos is not None:          # d rnn_out back into the [B, T] layout (zero at padded steps)
@@ -1367,7 +1268,7 @@ class NARModuleModel:
             else:
                 rt.gemm(pl.dFC1, p('Wf1'), pl.drnn, BT, Hp, 512, 512, 512, Hp, transB=1)
             if drop:
-                dropout(pl.drnn, pl.drnn, BTf, Hp, Hp, 20 + last, 20 + last, 1, None)
+                dropout.apply(pl.drnn, pl.drnn, BTf, Hp, Hp, SITE_RNN_OUT + last, SITE_RNN_OUT + last, 1, None)
             for l in range(last, -1, -1):
                 rnn.backward(pl, l, ss)
                 if l == 0:   # -> gradient w.r.t. the CAR tanh pre-activation of the clicked-input rows (main lane waits for it)
@@ -1425,81 +1326,29 @@ class NARModuleModel:
                     rt.gemm(pl.dxproj, p('rnn%d/Wx' % l), pl.drnn, BTf, Hp, NGH, NGH, NGH, Hp, transB=1)
                     rt.gemm(rnn_y(l - 1), pl.dxproj, g('rnn%d/Wx' % l), Hp, NGH, BTf, Hp, NGH, NGH, transA=1, splits=0)
                     if drop:
-                        dropout(pl.drnn, pl.drnn, BTf, Hp, Hp, 20 + l - 1, 20 + l - 1, 1, None)
+                        dropout.apply(pl.drnn, pl.drnn, BTf, Hp, Hp, SITE_RNN_OUT + l - 1, SITE_RNN_OUT + l - 1, 1, None)
                 rnn.wgrads(pl, l)
             if deferred_w2 is not None:
                 deferred_w2()
-        def precar_backward(ws):
-            """PreCAR combine scatter, W1 weight gradients, feature / embedding backward (on whatever lane is current)."""
-            st = _stream()
-            if drop:        # dense PreCAR backward: one weight gradient over all CAR rows, d(input rows) masked, then summed per
-                #             position / per item row by the same deterministic scatter as the factorised path (width Fc + Fi)
-                Fw = drop['Fw']
-                dZ1 = arm.dense_dZ1(pl, st)
-                rt.gemm(pl.Xd, dZ1, drop['gW1'], Fw, C, Rall, Fw, C, C, transA=1, splits=0)
-                rt.colsum(dZ1, C, Rall, C, g('b1'))
-                rt.gemm(dZ1, drop['W1'], pl.dXd, Rall, Fw, C, C, C, Fw, transB=1)
-                dropout(pl.dXd, pl.dXd, BT, Fw, Fw, 16, 16, 1, pos, Fc, Fc - L.f_ctx)
-                dropout(pl.dXd[BT:], pl.dXd[BT:], Rc, Fw, Fw, 17, 18, NC, pos, Fc, Fc - L.f_ctx)
-                check(lib.cham_combine_bwd(ptr(pl.dXd), Fw, BT, N, pmax, ptr(neg_slot), ptr(pl.dUx), ptr(pl.dVx), ptr(pl.drop_ws),
-                                           pl.drop_ws.numel() * 4, st), "cham_combine_bwd")
-                pl.dXc[:BT].copy_(pl.dUx[:BT, :Fc]); pl.dXi[:RV].copy_(pl.dVx[:RV, Fc:])
-            else:
-                arm.combine_bwd(pl, ws, st)
-            n_rows_cat = d['cat'].shape[1]
-
-            def feature_bwd(dX, Xraw, R, F, gname, bname):
-                # dgamma / dbeta column sums: the coalesced two-launch form through this lane's workspace (CHAM_FEATURE_BWD_WS=0: one workgroup per column)
-                if rt.feature_bwd_ws:
-                    wsl = rt._lane_ws('gemm_ws')
-                    check(lib.cham_feature_bwd_ws(ptr(dX), ptr(Xraw), R, F, ptr(g(gname)), ptr(g(bname)), ptr(wsl), wsl.numel() * 4, _stream()),
-                          "cham_feature_bwd_ws")
-                else:
-                    check(lib.cham_feature_bwd(ptr(dX), ptr(Xraw), R, F, ptr(g(gname)), ptr(g(bname)), _stream()), "cham_feature_bwd")
-
-            def ctx_chain():      # user-context half of the PreCAR input: weight gradient, bias, d(features), scale / center, embedding tables
-                if not drop:
-                    rt.gemm(pl.Xc_s, pl.dU, g('W1c'), Fc, C, BT, Fc, C, C, transA=1, splits=0)
-                    rt.colsum(pl.dU, C, BT, C, g('b1'))
-                    rt.gemm(pl.dU, p('W1c'), pl.dXc, BT, Fc, C, C, C, Fc, transB=1)
-                feature_bwd(pl.dXc, pl.Xc_raw, BT, Fc, 'gamma_ctx', 'beta_ctx')
-                for kind, feat, c0, dim, card, off in rt.ctx_emb_groups:
-                    check(lib.cham_emb_grad_scan(ptr(pl.dXc), BT, Fc, c0, dim, ptr(p('gamma_ctx')), d['cat'].data_ptr() + 8 * feat * n_rows_cat,
-                                                 None, card, rt.grads.data_ptr() + 4 * off, _stream()), "cham_emb_grad_scan")
-
-            def item_chain():     # item half
-                if not drop:
-                    rt.gemm(pl.Xi_s, pl.dV, g('W1i'), Fi, C, RV, Fi, C, C, transA=1, splits=0)
-                    rt.gemm(pl.dV, p('W1i'), pl.dXi, RV, Fi, C, C, C, Fi, transB=1)
-                feature_bwd(pl.dXi, pl.Xi_raw, RV, Fi, 'gamma_item', 'beta_item')
-                for kind, feat, c0, dim, card, off in rt.item_emb_groups:
-                    if kind == COL_ITEMEMB:
-                        if pl.grouped_ev is not None:
-                            torch.cuda.current_stream().wait_event(pl.grouped_ev)
-                        check(lib.cham_emb_grad_grouped(ptr(pl.dXi), RV, Fi, c0, dim, ptr(p('gamma_item')), ptr(pl.ids_all), ptr(pl.perm),
-                                                        ptr(pl.seg), rt.grads.data_ptr() + 4 * off, _stream()), "cham_emb_grad_grouped")
-                    else:
-                        check(lib.cham_emb_grad_scan(ptr(pl.dXi), RV, Fi, c0, dim, ptr(p('gamma_item')),
-                                                     rt.meta_cat.data_ptr() + 8 * feat * rt.n_items, ptr(pl.ids_all), card,
-                                                     rt.grads.data_ptr() + 4 * off, _stream()), "cham_emb_grad_scan")
-
-            # Round 6: the two halves are independent once dU / dV exist, and they are the SERIAL tail of the step - ~25 latency-bound launches
-            # behind the W2 weight gradient with the chip otherwise idle.  The user-context half goes to the third lane, the item half
-            # stays here (CHAM_TAIL_SPLIT=0: both on this lane, the order of rounds 1-5).  Same kernels, same arguments: same results.
-            if on and rt.tail_split and not drop and st == main_stream.cuda_stream:
-                e_duv = mark()
-                with aux(e_duv):
-                    ctx_chain()
-                    e_ctx = mark()
-                item_chain()
-                main_stream.wait_event(e_ctx)
-            else:
-                ctx_chain()
-                item_chain()
-
         if on:
             main_wait(e_dZ1in)
-        precar_backward(rt.gemm_ws)      # beside the W2 wgrad of the side lane
+        # PreCAR backward beside the W2 wgrad of the side lane: dZ1 -> the gradients at the layer's two inputs (combine scatter; dense form:
+        # + its weight gradient), then per half the W1 weight gradient, d(features), scale / center and the embedding tables (nar/input_rows.py)
+        st = _stream()
+        pre.backward(pl, rt.gemm_ws, st)
+        # Round 6: the two halves are independent once dU / dV exist, and they are the SERIAL tail of the step - ~25 latency-bound launches
+        # behind the W2 weight gradient with the chip otherwise idle.  The user-context half goes to the third lane, the item half
+        # stays here (CHAM_TAIL_SPLIT=0: both on this lane, the order of rounds 1-5).  Same kernels, same arguments: same results.
+        if on and rt.tail_split and not drop and st == main_stream.cuda_stream:
+            e_duv = mark()
+            with aux(e_duv):
+                pre.ctx_chain(pl)
+                e_ctx = mark()
+            pre.item_chain(pl)
+            main_stream.wait_event(e_ctx)
+        else:
+            pre.ctx_chain(pl)
+            pre.item_chain(pl)
         rt.join()
         if e_auxdone is not None:
             main_stream.wait_event(e_auxdone)

@@ -1,14 +1,16 @@
 """Launch trace of the training step (manual tool, not a test): proves that a change of the step DRIVER - the schedule in
-NARModuleModel._forward / backward, an arm of nar/candidate_rows.py, a launch path of nar/recurrent.py - left every launch, its order, its
-arguments and its lane as they were.
+NARModuleModel._forward / backward, an arm of nar/candidate_rows.py, a launch path of nar/recurrent.py, the feature rows or an input form
+of nar/input_rows.py - left every launch, its order, its arguments and its lane as they were.
 
 One configuration per process (the switches are read when the library / the runtime is created), traced under both schedules:
   short   as is: at these shapes Rc <= rt.w2_main_rows - W2 weight gradient on the main lane, cooperative recurrent kernels, no head split
   full    rt.w2_main_rows = 0, rt.rnn_coop_rows = -1: third lane, deferred W2 weight gradient, head split, single-workgroup recurrent kernels
-Each run = four optimizer steps + one evaluate_step on five synthetic batches (device-resident state, presampled negatives).  rt.lib and the
-state's lib are replaced by a proxy that writes one line per library call of steps 2 onward: the entry point, every non-pointer argument by value,
-every pointer argument (_lib._SIGNATURES says which) renamed by order of first appearance - p0, p1, ..., 0 for NULL.  The stream is a pointer
-argument, so its tag names the lane.  The run ends with the SHA-1 of the stacked losses and of rt.flat / m / v / grads.
+Each run = four optimizer steps + one evaluate_step on five synthetic batches (device-resident state, presampled negatives; the configurations
+in HOST_STATE feed the host's ClickedItemsState instead - the only way to cham_norm_stats_from_recent).  rt.lib and the state's lib are replaced
+by a proxy that writes one line per library call of every step - the first one included: it builds the plan and, with an empty state, takes the
+normalisation statistics from the batch's own rows - with the entry point, every non-pointer argument by value, every pointer argument
+(_lib._SIGNATURES says which) renamed by order of first appearance - p0, p1, ..., 0 for NULL.  The stream is a pointer argument, so its tag names
+the lane.  The run ends with the SHA-1 of the stacked losses and of rt.flat / m / v / grads.
 
 The script touches rt.lib and _SIGNATURES only, so the same file runs on any two commits:
   python scripts/launch_trace.py --list
@@ -53,7 +55,10 @@ CONFIGS = {
     'lstm2': ({}, {'rnn_cell': 'lstm', 'H': 400, 'rnn_num_layers': 2}, {}, 'g1', 0),
     'full_length': ({}, {}, {}, 'full', 0),
     'microbatched': ({}, {}, {}, 'g1', 8),
+    'host_state': ({}, {}, {}, 'g1', 0),                                                   # recent clicks uploaded from the host every step
+    'item_elem': ({}, {}, {'item_lds': False}, 'g1', 0),                                   # item rows by the one-thread-per-element assemble
 }
+HOST_STATE = {'host_state'}
 SCHEDULES = {'short': {}, 'full': {'w2_main_rows': 0, 'rnn_coop_rows': -1}}
 B, SEQ, N_ITEMS = 16, 6, 1000
 
@@ -98,7 +103,7 @@ def run(cfg, schedule):
     import torch
     from chameleon_recsys_amd import _lib
     from chameleon_recsys_amd.nar import synthetic
-    from chameleon_recsys_amd.nar.clicked_items_state import DeviceClickedItemsState
+    from chameleon_recsys_amd.nar.clicked_items_state import ClickedItemsState, DeviceClickedItemsState
     from chameleon_recsys_amd.nar.nar_model import ModeKeys, NARModuleModel, NARRuntime
     from tests import helpers as H
     _env, over, attrs, length_dist, micro = CONFIGS[cfg]
@@ -120,26 +125,35 @@ def run(cfg, schedule):
     for k, v in list(attrs.items()) + list(SCHEDULES[schedule].items()):
         assert hasattr(rt, k), k
         setattr(rt, k, v)
-    st = DeviceClickedItemsState(p['recent_clicks_buffer_hours'], p['recent_clicks_buffer_max_size'], p['recent_clicks_for_normalization'], N_ITEMS)
+    host = cfg in HOST_STATE
+    st = (ClickedItemsState if host else DeviceClickedItemsState)(p['recent_clicks_buffer_hours'], p['recent_clicks_buffer_max_size'],
+                                                                  p['recent_clicks_for_normalization'], N_ITEMS)
     tr = Trace()
     rt.lib = LibProxy(rt.lib, tr, _lib._SIGNATURES)
-    st.lib = LibProxy(st.lib, tr, _lib._SIGNATURES)
+    if not host:
+        st.lib = LibProxy(st.lib, tr, _lib._SIGNATURES)
     batches = synthetic.make_batches(5, B, SEQ, N_ITEMS, p['session_features_config'], length_dist=length_dist)
     dev = [model.upload_batch(f, l) for f, l in batches]
     losses = []
     for i, d in enumerate(dev):
-        tr.on = i >= 1
-        tr.lines.append('# step %d' % (i + 1)) if tr.on else None
+        tr.on = True
+        tr.lines.append('# step %d' % (i + 1))
         m = model if i < 4 else ev
-        m.feed_state(st, st)
+        if host:
+            m.feed_state(st.get_articles_recent_pop_norm().copy(), st.get_recent_clicks_buffer().copy())
+        else:
+            m.feed_state(st, st)
         if i == 4:
             losses.append(m.evaluate_step(d).clone())
         elif micro:
             losses.append(m.train_step_microbatched(batches[i][0], batches[i][1], micro).clone())
         else:
             losses.append(m.train_step(d).clone())
-        st.update_from_device_batch(d['aci'], d['g_event_ts'])
-        if i + 1 < 4 and not micro:
+        if host:
+            H.update_state(st, *batches[i])
+        else:
+            st.update_from_device_batch(d['aci'], d['g_event_ts'])
+        if i + 1 < 4 and not micro and not host:
             model.presample(dev[i + 1])
     torch.cuda.synchronize()
     tr.on = False

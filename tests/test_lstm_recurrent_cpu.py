@@ -8,7 +8,8 @@ import torch
 
 from chameleon_recsys_amd.nar import recurrent
 from chameleon_recsys_amd.nar.recurrent import StepwiseLstm, StepwiseUgrnn
-from tests.test_recurrent_cpu import B, F32, S, T, WG, Recorder, layout
+from tests.recording import Recorder, S
+from tests.test_recurrent_cpu import B, F32, T, WG, layout
 
 
 def make(units, layers=1):
