@@ -141,24 +141,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p) {
     float* As = smem;                 // [2][BK][LDA]
     float* Bs = smem + 2 * ASZ;       // [2][BK][LDB]   (2*ASZ*4 bytes is a multiple of 16 for every instance)
 
-    // ---- XCD-aware, bijective tile mapping (all scalar) --------------------------------------------
-    const int nwg = p.nbm * p.nbn;
     int tile_m, tile_n, split;
-    if (p.xcd_split) {
-        // split-K with a small output (wgrad): ALL tiles of one K-split on the same XCD, so that each K-panel of A and B is
-        // fetched from HBM once and shared through that XCD's L2 (tile-major placement re-read every panel on ~3 XCDs: the W2
-        // wgrad fetched 6.3 GB for 2.07 GB of operands).  Workgroups are dealt to the 8 XCDs round-robin in dispatch order.
-        const int lin = blockIdx.x + gridDim.x * blockIdx.y, slot = lin >> 3;
-        split = (lin & 7) + 8 * (slot / nwg);
-        const int t = slot % nwg;
-        tile_m = t / p.nbn; tile_n = t % p.nbn;
-    } else {
-        const int id = blockIdx.x;
-        const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-        const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-        tile_m = swz / p.nbn; tile_n = swz % p.nbn;
-        split = blockIdx.y;
-    }
+    gemm_tile_map(p, tile_m, tile_n, split);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int kbeg = split * p.kchunk;
     const int kend = min(p.K, kbeg + p.kchunk);
@@ -280,23 +264,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_kernel(GemmParams p) {
     __bf16* As = reinterpret_cast<__bf16*>(smem);      // [2][BM][LDK]
     __bf16* Bs = As + 2 * ASZ;                         // [2][BN][LDK]
 
-    const int nwg = p.nbm * p.nbn;
     int tile_m, tile_n, split;
-    if (p.xcd_split) {
-        // split-K with a small output (wgrad): ALL tiles of one K-split on the same XCD, so that each K-panel of A and B is
-        // fetched from HBM once and shared through that XCD's L2 (tile-major placement re-read every panel on ~3 XCDs: the W2
-        // wgrad fetched 6.3 GB for 2.07 GB of operands).  Workgroups are dealt to the 8 XCDs round-robin in dispatch order.
-        const int lin = blockIdx.x + gridDim.x * blockIdx.y, slot = lin >> 3;
-        split = (lin & 7) + 8 * (slot / nwg);
-        const int t = slot % nwg;
-        tile_m = t / p.nbn; tile_n = t % p.nbn;
-    } else {
-        const int id = blockIdx.x;
-        const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-        const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-        tile_m = swz / p.nbn; tile_n = swz % p.nbn;
-        split = blockIdx.y;
-    }
+    gemm_tile_map(p, tile_m, tile_n, split);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int kbeg = split * p.kchunk;
     const int kend = min(p.K, kbeg + p.kchunk);

@@ -19,28 +19,10 @@
 //     as [row][k] (row stride BK + 8 halves: conflict-free ds_read_b128 fragments); free-contiguous operands (TN) land as [k][row]
 //     and the fragments - 8 consecutive k of one row per lane - are gathered by the LDS transpose read ds_read_b64_tr_b16
 //     (two per fragment; layout verified on the device: tests/probe/tr_probe.hip).
-//   * buffer-descriptor windows, XCD-aware tile swizzle and the one-K-split-per-XCD placement as in gemm.hip.
-#include "common.h"
+//   * buffer-descriptor windows, XCD-aware tile swizzle and the one-K-split-per-XCD placement of gemm_shared.h.
+#define GEMM_SHARED_NO_SPLITK_REDUCE          /* gemm_b16_splitk_reduce[_wide] below */
+#include "gemm_shared.h"
 #include <stdlib.h>
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-#define OOB_OFF 0x80000000u
-#define WINDOW_BYTES 0x7FFFF000
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t b16_window(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, WINDOW_BYTES, 0x00020000);
-}
-__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-__device__ __forceinline__ unsigned pack_bf2(float a, float b) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v; v[0] = (__bf16)a; v[1] = (__bf16)b;           // v_cvt_pk_bf16_f32 (round to nearest even)
-    return __builtin_bit_cast(unsigned, v);
-}
 
 struct B16Params {
     const __bf16* A; const __bf16* B; void* C;
@@ -124,12 +106,6 @@ __device__ __forceinline__ bf16x8 frag_read(const __bf16* __restrict__ S, int f0
     }
 }
 
-template <int ACT> __device__ __forceinline__ float b16_act(float v) {
-    if (ACT == ACT_LEAKY) return v > 0.f ? v : 0.2f * v;
-    if (ACT == ACT_TANH) return cham_tanhf(v);
-    return v;
-}
-
 // EPI: 0 plain (fp32 out: optional accumulate), 1 bias+leaky, 2 bias+tanh, 3 x leaky'(dref), 4 x tanh'(dref), 5 bias, 6 split-K partial
 // MINW: __launch_bounds__ second argument = waves per SIMD the register allocation must leave room for (1 = no constraint)
 template <int BM, int BN, int WM, int WN, int BK, int MINW, bool AK, bool BKC, int EPI, bool OUTF32>
@@ -142,20 +118,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm_b16_kernel(B16Params 
     __bf16* As = reinterpret_cast<__bf16*>(smem_raw);        // [2][ASZ]
     __bf16* Bs = As + 2 * ASZ;                               // [2][BSZ]   (2 * ASZ * 2 bytes is a multiple of 16)
 
-    const int nwg = p.nbm * p.nbn;
     int tile_m, tile_n, split;
-    if (p.xcd_split) {          // all tiles of one K-split on one XCD (gemm.hip, same reasoning)
-        const int lin = blockIdx.x + gridDim.x * blockIdx.y, slot = lin >> 3;
-        split = (lin & 7) + 8 * (slot / nwg);
-        const int t = slot % nwg;
-        tile_m = t / p.nbn; tile_n = t % p.nbn;
-    } else {                    // XCD-aware bijective swizzle: consecutive tile ids (same A panel) share an XCD's L2
-        const int id = blockIdx.x;
-        const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-        const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-        tile_m = swz / p.nbn; tile_n = swz % p.nbn;
-        split = blockIdx.y;
-    }
+    gemm_tile_map(p, tile_m, tile_n, split);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int kbeg = split * p.kchunk, kend = min(p.K, kbeg + p.kchunk);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -177,8 +141,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm_b16_kernel(B16Params 
     lb.init(p.ldb, p.N - n0);
     const int nk = (kend - kbeg + BK - 1) / BK;
     if (nk > 0) {
-        la.load(b16_window(aw), kend - kbeg);
-        lb.load(b16_window(bw), kend - kbeg);
+        la.load(make_window(aw), kend - kbeg);
+        lb.load(make_window(bw), kend - kbeg);
         la.store(As); lb.store(Bs);
     }
     __syncthreads();
@@ -187,8 +151,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm_b16_kernel(B16Params 
         if (kt + 1 < nk) {          // tile kt+1: loads fly behind this tile's MFMAs
             aw += astep; bw += bstep;
             const int k0 = kbeg + (kt + 1) * BK;
-            la.load(b16_window(aw), kend - k0);
-            lb.load(b16_window(bw), kend - k0);
+            la.load(make_window(aw), kend - k0);
+            lb.load(make_window(bw), kend - k0);
         }
         const __bf16* Ac = As + cur * ASZ;
         const __bf16* Bc = Bs + cur * BSZ;
@@ -219,9 +183,9 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm_b16_kernel(B16Params 
     char* cbase = (EPI == 6) ? reinterpret_cast<char*>(p.partial + ((size_t)split * p.M + m0) * p.N + n0)
                              : reinterpret_cast<char*>(p.C) + ((size_t)m0 * p.ldc + n0) * (F32 ? 4 : 2);
     const unsigned ldc = (EPI == 6) ? (unsigned)p.N : (unsigned)p.ldc;
-    const __amdgpu_buffer_rsrc_t cw = b16_window(cbase);
-    const __amdgpu_buffer_rsrc_t dw = b16_window((EPI == 3 || EPI == 4) ? reinterpret_cast<const char*>(p.dref + (size_t)m0 * p.ldr + n0) : cbase);
-    const __amdgpu_buffer_rsrc_t biasw = b16_window((EPI == 1 || EPI == 2 || EPI == 5) ? reinterpret_cast<const char*>(p.bias + n0) : cbase);
+    const __amdgpu_buffer_rsrc_t cw = make_window(cbase);
+    const __amdgpu_buffer_rsrc_t dw = make_window((EPI == 3 || EPI == 4) ? reinterpret_cast<const char*>(p.dref + (size_t)m0 * p.ldr + n0) : cbase);
+    const __amdgpu_buffer_rsrc_t biasw = make_window((EPI == 1 || EPI == 2 || EPI == 5) ? reinterpret_cast<const char*>(p.bias + n0) : cbase);
     const bool accum = (EPI == 0) && F32 && p.accumulate;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -239,10 +203,10 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm_b16_kernel(B16Params 
                     v[0] += __uint_as_float(bv.x); v[1] += __uint_as_float(bv.y); v[2] += __uint_as_float(bv.z); v[3] += __uint_as_float(bv.w);
                     if (EPI == 1) {
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) v[t] = b16_act<ACT_LEAKY>(v[t]);
+                        for (int t = 0; t < 4; ++t) v[t] = act_fwd_c<ACT_LEAKY>(v[t]);
                     } else if (EPI == 2) {
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) v[t] = b16_act<ACT_TANH>(v[t]);
+                        for (int t = 0; t < 4; ++t) v[t] = act_fwd_c<ACT_TANH>(v[t]);
                     }
                 }
                 if (EPI == 3 || EPI == 4) {

@@ -16,8 +16,8 @@
 //   NT  C[M,N] = epi(A[M,K] B[N,K]^T)    planes k-contiguous: CAR forward (B = planes of W2^T), CAR dgrad (B = planes of W2)
 //   TN  C[M,N] = A[K,M]^T B[K,N]         planes with the FREE index contiguous (W2 wgrad: Z1^T dZ2, K = candidate rows); split-K
 //
-// Core = the LDS-DMA core of gemm_p3.hip (256 x 256 x 16 tile, 8 waves as 2 x 4, 4 x 2 MFMA tiles of 32x32x16 per wave, slabs of
-// 8 KB with the same source-side swizzles, `buffer_load_dwordx4 ... lds`), re-cut for four slabs per 16-k chunk:
+// Core = the LDS-DMA core of gemm_dma.h (256 x 256 x 16 tile, 8 waves as 2 x 4, 4 x 2 MFMA tiles of 32x32x16 per wave, slabs of
+// 8 KB with gemm_p3.hip's source-side swizzles, `buffer_load_dwordx4 ... lds`), cut for four slabs per 16-k chunk:
 //   stage = (A_h, A_l, B_h, B_l) = 32 KB; ring of FOUR stages = 128 KB of LDS, one workgroup per CU.
 //   step i (slot i & 3):
 //     top   DMA of chunk i + 3 into slot (i + 3) & 3 (its last reader was P0 of step i - 1, separated by that step's barrier)
@@ -30,10 +30,9 @@
 //   fragment registers.  A request has 2.5 steps (~3 800 cycles at two waves per SIMD) to land.
 // Epilogues: x 1/(s_a s_b), then plain | + bias | + bias -> tanh (CAR forward) | x leaky'(sign of the saved activation's h plane) (CAR
 // dgrad) | split-K partial (wgrad; partials are stored unscaled-back, i.e. in true units: the shared fixed-order reduction adds them).
-#include "gemm_shared.h"
+#include "gemm_dma.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef short h2_s16x4 __attribute__((ext_vector_type(4)));
 
 struct H2Params {
     const _Float16* A; const _Float16* B;      // plane 0 (h) of each operand; plane 1 (l) `*_ps` elements further
@@ -61,13 +60,6 @@ struct H2Params {
 #define H2_STAGE (4 * H2_SLAB)
 #define H2_RING 4
 
-__device__ __forceinline__ u32x4 h2_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    u32x4 r;
-    r.x = (unsigned)a; r.y = (unsigned)(a >> 32) & 0xFFFFu; r.z = bytes; r.w = 0x00020000u;
-    return r;
-}
-
 // four LDS-DMA requests of one stage: 16 bytes per lane, LDS destination = M0 + lane * 16 (wave-uniform), source = descriptor base +
 // voffset (per lane; the K advance is part of it so that the descriptor's range check sees it).  M0 is compiler-reserved: saved and
 // restored inside the statement (cdna_hip_programming.md 5.7).
@@ -86,32 +78,6 @@ __device__ __forceinline__ void h2_dma_stage(unsigned lds0, unsigned va, unsigne
         : "=&s"(keep)
         : "s"(lds0), "s"(l1), "s"(l2), "s"(l3), "v"(va), "v"(vb), "s"(ra0), "s"(ra1), "s"(rb0), "s"(rb1)
         : "memory");
-}
-
-// (TN: `hi` = byte distance of k-row + 4 in the slab image: 4 * 512 for a row-major operand's image, 4 * 64 for a tile-blocked one's)
-template <bool TN>
-__device__ __forceinline__ half8 h2_frag(const unsigned char* __restrict__ s, unsigned hi_off = 4 * 512) {
-    if constexpr (!TN) {
-        return *reinterpret_cast<const half8*>(s);
-    } else {
-        typedef __attribute__((address_space(3))) h2_s16x4 lds_s4;
-        const h2_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(s));
-        const h2_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(s + hi_off));
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        s16x8 v;
-        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-        return __builtin_bit_cast(half8, v);
-    }
-}
-
-// LDS-only barrier: builtins so that the wait-count pass sees the drain; vmcnt is handled by hand (the DMA requests are invisible to
-// the compiler).
-__device__ __forceinline__ void h2_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 // acc[i][j][e] = element (row wm0 + 32 i + (e & 3) + 8 (e >> 2) + 4 kl, column wn0 + 32 j + fl) of the tile at (m0, n0)
@@ -257,11 +223,7 @@ __device__ __forceinline__ void h2_epilogue(const H2Params& p, floatx16 (&acc)[T
         }
         if (gs) emit();
     } else {
-        GemmParams g;
-        g.A = nullptr; g.B = nullptr; g.C = p.C; g.M = p.M; g.N = p.N; g.K = p.K; g.lda = 0; g.ldb = 0; g.ldc = p.ldc;
-        g.bias = p.bias; g.act = ACT_NONE; g.dref = nullptr; g.ldr = 0; g.dact = ACT_NONE; g.rs = nullptr; g.ldrs = 0; g.rs_div = 1;
-        g.accumulate = p.accumulate; g.kchunk = p.kchunk; g.splits = p.splits; g.partial = p.partial; g.nbm = p.nbm; g.nbn = p.nbn; g.xcd_split = p.xcd_split;
-        gemm_epilogue<EPI, TM, TNN>(g, acc, m0, n0, wm0, wn0, split, kl, fl);
+        gemm_epilogue<EPI, TM, TNN>(epilogue_params(p, p.bias), acc, m0, n0, wm0, wn0, split, kl, fl);
     }
 }
 
@@ -275,20 +237,8 @@ __global__ __launch_bounds__(512) void gemm_h2_kernel(H2Params p) {
     constexpr int BM = 256, BN = 256, BK = 16, TM = 4, TNN = 2;
     extern __shared__ __attribute__((aligned(1024))) unsigned char h2_smem[];
 
-    const int nwg = p.nbm * p.nbn;
     int tile_m, tile_n, split;
-    if (p.xcd_split) {                                 // one K-split per XCD (gemm.hip): every K panel is fetched from HBM once
-        const int lin = blockIdx.x + gridDim.x * blockIdx.y, slot = lin >> 3;
-        split = (lin & 7) + 8 * (slot / nwg);
-        const int t = slot % nwg;
-        tile_m = t / p.nbn; tile_n = t % p.nbn;
-    } else {                                           // XCD-aware bijective swizzle: the column tiles of an A panel share an L2
-        const int id = blockIdx.x;
-        const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-        const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-        tile_m = swz / p.nbn; tile_n = swz % p.nbn;
-        split = blockIdx.y;
-    }
+    gemm_tile_map(p, tile_m, tile_n, split);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int kbeg = split * p.kchunk;
     const int kend = min(p.K, kbeg + p.kchunk);
@@ -308,8 +258,8 @@ __global__ __launch_bounds__(512) void gemm_h2_kernel(H2Params p) {
         const size_t abytes = aall > koff ? aall - koff : 0, bbytes = ball > koff ? ball - koff : 0;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            ra[q] = h2_rsrc(p.A + q * p.a_ps + (size_t)m0 * p.lda + kbeg, (unsigned)min(abytes, (size_t)0xFFFFFFF0u));
-            rb[q] = h2_rsrc(p.B + q * p.b_ps + (size_t)n0 * p.ldb + kbeg, (unsigned)min(bbytes, (size_t)0xFFFFFFF0u));
+            ra[q] = dma_rsrc(p.A + q * p.a_ps + (size_t)m0 * p.lda + kbeg, (unsigned)min(abytes, (size_t)0xFFFFFFF0u));
+            rb[q] = dma_rsrc(p.B + q * p.b_ps + (size_t)n0 * p.ldb + kbeg, (unsigned)min(bbytes, (size_t)0xFFFFFFF0u));
         }
         // lane l of wave w fills LDS piece (row 32 w + l / 2, half l & 1); that piece holds source half (l & 1) ^ bit 3 of the row
         const int row = 32 * wave + (lane >> 1), half = (lane & 1) ^ ((lane >> 4) & 1);
@@ -336,12 +286,12 @@ __global__ __launch_bounds__(512) void gemm_h2_kernel(H2Params p) {
             const size_t t0 = (size_t)(kbeg >> 8), all = ((size_t)p.a_tiles - t0) * tba, skip = (size_t)(m0 >> 5) * (H2B_BLOCK * 2);
 #pragma unroll
             for (int q = 0; q < 2; ++q)
-                ra[q] = h2_rsrc(p.A + q * p.a_ps + (t0 * (size_t)(p.lda >> 5) + (size_t)(m0 >> 5)) * H2B_BLOCK, (unsigned)min(all > skip ? all - skip : (size_t)0, (size_t)0xFFFFFFF0u));
+                ra[q] = dma_rsrc(p.A + q * p.a_ps + (t0 * (size_t)(p.lda >> 5) + (size_t)(m0 >> 5)) * H2B_BLOCK, (unsigned)min(all > skip ? all - skip : (size_t)0, (size_t)0xFFFFFFF0u));
             va = (unsigned)wave * (unsigned)(H2B_BLOCK * 2) + (unsigned)lane * 16u;       // wave w: column block w, 16 k-rows x 64 bytes = 1 KB CONTIGUOUS
         } else {
 #pragma unroll
             for (int q = 0; q < 2; ++q)      // (M, N multiples of 256: the m / n extent of a tile never leaves its k-row)
-                ra[q] = h2_rsrc(p.A + q * p.a_ps + (size_t)kbeg * p.lda + m0, (unsigned)min(abytes > (size_t)m0 * 2 ? abytes - (size_t)m0 * 2 : (size_t)0, (size_t)0xFFFFFFF0u));
+                ra[q] = dma_rsrc(p.A + q * p.a_ps + (size_t)kbeg * p.lda + m0, (unsigned)min(abytes > (size_t)m0 * 2 ? abytes - (size_t)m0 * 2 : (size_t)0, (size_t)0xFFFFFFF0u));
             va = ((unsigned)k * (unsigned)p.lda + 8u * j) * 2u;
         }
         if (p.b_tiles > 0) {
@@ -349,12 +299,12 @@ __global__ __launch_bounds__(512) void gemm_h2_kernel(H2Params p) {
             const size_t t0 = (size_t)(kbeg >> 8), all = ((size_t)p.b_tiles - t0) * tbb, skip = (size_t)(n0 >> 5) * (H2B_BLOCK * 2);
 #pragma unroll
             for (int q = 0; q < 2; ++q)
-                rb[q] = h2_rsrc(p.B + q * p.b_ps + (t0 * (size_t)(p.ldb >> 5) + (size_t)(n0 >> 5)) * H2B_BLOCK, (unsigned)min(all > skip ? all - skip : (size_t)0, (size_t)0xFFFFFFF0u));
+                rb[q] = dma_rsrc(p.B + q * p.b_ps + (t0 * (size_t)(p.ldb >> 5) + (size_t)(n0 >> 5)) * H2B_BLOCK, (unsigned)min(all > skip ? all - skip : (size_t)0, (size_t)0xFFFFFFF0u));
             vb = (unsigned)wave * (unsigned)(H2B_BLOCK * 2) + (unsigned)lane * 16u;
         } else {
 #pragma unroll
             for (int q = 0; q < 2; ++q)
-                rb[q] = h2_rsrc(p.B + q * p.b_ps + (size_t)kbeg * p.ldb + n0, (unsigned)min(bbytes > (size_t)n0 * 2 ? bbytes - (size_t)n0 * 2 : (size_t)0, (size_t)0xFFFFFFF0u));
+                rb[q] = dma_rsrc(p.B + q * p.b_ps + (size_t)kbeg * p.ldb + n0, (unsigned)min(bbytes > (size_t)n0 * 2 ? bbytes - (size_t)n0 * 2 : (size_t)0, (size_t)0xFFFFFFF0u));
             vb = ((unsigned)k * (unsigned)p.ldb + 8u * j) * 2u;
         }
         stepa = (unsigned)BK * (unsigned)p.lda * 2u; stepb = (unsigned)BK * (unsigned)p.ldb * 2u;
@@ -373,7 +323,7 @@ __global__ __launch_bounds__(512) void gemm_h2_kernel(H2Params p) {
         return 16 * c < klim ? vb + (r >> 8) * tbb + (r & 255u) * 64u : 0x80000000u;
     };
 
-    // ---- per-lane fragment offsets inside a slab (gemm_p3.hip's layouts: 16-bit elements, the element type does not matter)
+    // ---- per-lane fragment offsets inside a slab (gemm_p3.hip's layouts)
     unsigned fa[TM], fb[TNN];
     if constexpr (!TN) {
         const int l31 = lane & 31;
@@ -426,12 +376,12 @@ __global__ __launch_bounds__(512) void gemm_h2_kernel(H2Params p) {
         for (int s = 0; s < 3; ++s)
             h2_dma_stage(lds_base + (unsigned)s * H2_STAGE + wave_off, chunk_a(s), chunk_b(s), ra[0], ra[1], rb[0], rb[1]);
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        h2_barrier();
+        dma_barrier();
         {   // early fragments of chunk 0
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) BH[j] = h2_frag<TN>(h2_smem + 2 * H2_SLAB + fb[j], hib);
+            for (int j = 0; j < TNN; ++j) BH[j] = dma_frag<half8, TN>(h2_smem + 2 * H2_SLAB + fb[j], hib);
 #pragma unroll
-            for (int i = 0; i < TM; ++i) AL[i] = h2_frag<TN>(h2_smem + 1 * H2_SLAB + fa[i], hia);
+            for (int i = 0; i < TM; ++i) AL[i] = dma_frag<half8, TN>(h2_smem + 1 * H2_SLAB + fa[i], hia);
         }
         int cur = 0;                                    // slot of chunk i
         for (int i = 0; i < nk; ++i) {
@@ -444,21 +394,21 @@ __global__ __launch_bounds__(512) void gemm_h2_kernel(H2Params p) {
             __builtin_amdgcn_sched_barrier(0);
             // P0: A_l x B_h; late fragments of this chunk
 #pragma unroll
-            for (int ii = 0; ii < TM; ++ii) AH[ii] = h2_frag<TN>(Sc + 0 * H2_SLAB + fa[ii], hia);
+            for (int ii = 0; ii < TM; ++ii) AH[ii] = dma_frag<half8, TN>(Sc + 0 * H2_SLAB + fa[ii], hia);
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) BL[j] = h2_frag<TN>(Sc + 3 * H2_SLAB + fb[j], hib);
+            for (int j = 0; j < TNN; ++j) BL[j] = dma_frag<half8, TN>(Sc + 3 * H2_SLAB + fb[j], hib);
             mma(AL, BH);
             // P1: A_h x B_h
             mma(AH, BH);
             // mid: this wave's requests for chunk i + 1 have landed (the eight of chunks i + 2, i + 3 stay in flight); after the barrier
             // every wave's have
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            h2_barrier();
+            dma_barrier();
             // P2: A_h x B_l; early fragments of chunk i + 1 into the registers that are dead
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) BH[j] = h2_frag<TN>(Sn + 2 * H2_SLAB + fb[j], hib);
+            for (int j = 0; j < TNN; ++j) BH[j] = dma_frag<half8, TN>(Sn + 2 * H2_SLAB + fb[j], hib);
 #pragma unroll
-            for (int ii = 0; ii < TM; ++ii) AL[ii] = h2_frag<TN>(Sn + 1 * H2_SLAB + fa[ii], hia);
+            for (int ii = 0; ii < TM; ++ii) AL[ii] = dma_frag<half8, TN>(Sn + 1 * H2_SLAB + fa[ii], hia);
             mma(AH, BL);
             cur = nxt;
         }
@@ -490,24 +440,6 @@ __global__ __launch_bounds__(512) void gemm_h2_kernel(H2Params p) {
 #define H2W_SLAB 16384
 #define H2W_BUF (4 * H2W_SLAB)
 
-// four requests: (r0 @ v0 -> l0), (r0 @ v1 -> l0 + 1024), (r1 @ v0 -> l1), (r1 @ v1 -> l1 + 1024): the two 16-row halves of a wave's
-// 32 rows in the h plane's slab and in the l plane's slab
-__device__ __forceinline__ void h2w_dma4(unsigned l0, unsigned l1, unsigned v0, unsigned v1, const u32x4& r0, const u32x4& r1) {
-    unsigned keep;
-    const unsigned l0b = l0 + 1024u, l1b = l1 + 1024u;
-    asm volatile(
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %7, 0 offen lds\n\t"
-        "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %7, 0 offen lds\n\t"
-        "s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %8, 0 offen lds\n\t"
-        "s_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %8, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "s"(l0), "s"(l0b), "s"(l1), "s"(l1b), "v"(v0), "v"(v1), "s"(r0), "s"(r1)
-        : "memory");
-}
-
 // EPI: 0 plain, 2 bias + tanh, 3 x leaky'(dref h plane), 5 bias
 // ABLK (round 6): A is TILE-BLOCKED (common.h h2b_index) - the 256 rows of this workgroup are one row tile, double chunk D_j is its column
 // block j: 16 KB contiguous per plane, a request (16 rows x 64 bytes) is 1 KB of eight WHOLE 128-byte lines where the row-major operand
@@ -518,11 +450,8 @@ __global__ __launch_bounds__(512) void gemm_h2w_kernel(H2Params p) {
     constexpr int BM = 256, BN = 256, TM = 4, TNN = 2;
     extern __shared__ __attribute__((aligned(1024))) unsigned char h2_smem[];
 
-    const int nwg = p.nbm * p.nbn;
-    const int id = blockIdx.x;
-    const int q8 = nwg / 8, rr = nwg % 8, xcd = id % 8;       // XCD-aware bijective swizzle: the column tiles of an A panel share an L2
-    const int swz = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + id / 8;
-    const int tile_m = swz / p.nbn, tile_n = swz % p.nbn;
+    int tile_m, tile_n, split;
+    gemm_tile_map<false>(p, tile_m, tile_n, split);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int nd = p.K >> 5;                                   // double chunks
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -533,10 +462,10 @@ __global__ __launch_bounds__(512) void gemm_h2w_kernel(H2Params p) {
     const size_t aall = (size_t)max(p.M - m0, 0) * p.lda * 2, ball = (size_t)max(p.N - n0, 0) * p.ldb * 2;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        if constexpr (ABLK) ra[q] = h2_rsrc(p.A + q * p.a_ps + (size_t)tile_m * (size_t)(p.lda >> 5) * H2B_BLOCK,
+        if constexpr (ABLK) ra[q] = dma_rsrc(p.A + q * p.a_ps + (size_t)tile_m * (size_t)(p.lda >> 5) * H2B_BLOCK,
                                             (unsigned)min((size_t)(p.lda >> 5) * (H2B_BLOCK * 2), (size_t)0xFFFFFFF0u));      // this row tile (allocated whole)
-        else ra[q] = h2_rsrc(p.A + q * p.a_ps + (size_t)m0 * p.lda, (unsigned)min(aall, (size_t)0xFFFFFFF0u));
-        rb[q] = h2_rsrc(p.B + q * p.b_ps + (size_t)n0 * p.ldb, (unsigned)min(ball, (size_t)0xFFFFFFF0u));
+        else ra[q] = dma_rsrc(p.A + q * p.a_ps + (size_t)m0 * p.lda, (unsigned)min(aall, (size_t)0xFFFFFFF0u));
+        rb[q] = dma_rsrc(p.B + q * p.b_ps + (size_t)n0 * p.ldb, (unsigned)min(ball, (size_t)0xFFFFFFF0u));
     }
     // lane l of wave w, request half r: LDS piece (row 32 w + 16 r + l / 4, piece l & 3) <- source piece (l & 3) ^ ((row >> 2) & 3),
     // and (row >> 2) & 3 == (l >> 4) & 3 for every w, r
@@ -546,8 +475,7 @@ __global__ __launch_bounds__(512) void gemm_h2w_kernel(H2Params p) {
     constexpr unsigned stepA = ABLK ? (unsigned)(H2B_BLOCK * 2) : 64u;          // bytes from a double chunk to the next
     unsigned vb0 = (row * (unsigned)p.ldb + 8u * sp) * 2u, vb1 = vb0 + 16u * (unsigned)p.ldb * 2u;
 
-    // ---- per-lane fragment offsets inside a slab, k-half 0 (half 1: ^ 32)
-    unsigned fa0[TM], fb0[TNN], fa1[TM], fb1[TNN];
+    unsigned fa0[TM], fb0[TNN], fa1[TM], fb1[TNN];             // fragment offsets inside a slab: k-half 0, k-half 1 (^ 32)
     {
         const int l31 = lane & 31;
         const unsigned fo = (unsigned)l31 * 64u + (unsigned)((lane >> 5) ^ ((l31 >> 2) & 3)) * 16u;
@@ -578,11 +506,11 @@ __global__ __launch_bounds__(512) void gemm_h2w_kernel(H2Params p) {
         __builtin_amdgcn_sched_barrier(0);
     };
     auto dma_a = [&](unsigned buf) {          // (A_h, A_l) of the next double chunk of A
-        h2w_dma4(lds_base + buf + 0 * H2W_SLAB + wave_off, lds_base + buf + 1 * H2W_SLAB + wave_off, va0, va1, ra[0], ra[1]);
+        dma4(lds_base + buf + 0 * H2W_SLAB + wave_off, lds_base + buf + 1 * H2W_SLAB + wave_off, va0, va1, ra[0], ra[1]);
         va0 += stepA; va1 += stepA;
     };
     auto dma_b = [&](unsigned buf) {          // (B_h, B_l)
-        h2w_dma4(lds_base + buf + 2 * H2W_SLAB + wave_off, lds_base + buf + 3 * H2W_SLAB + wave_off, vb0, vb1, rb[0], rb[1]);
+        dma4(lds_base + buf + 2 * H2W_SLAB + wave_off, lds_base + buf + 3 * H2W_SLAB + wave_off, vb0, vb1, rb[0], rb[1]);
         vb0 += 64u; vb1 += 64u;
     };
 
@@ -595,7 +523,7 @@ __global__ __launch_bounds__(512) void gemm_h2w_kernel(H2Params p) {
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        h2_barrier();
+        dma_barrier();
         {   // early fragments of chunk 0
 #pragma unroll
             for (int j = 0; j < TNN; ++j) BH[j] = *reinterpret_cast<const half8*>(h2_smem + 2 * H2W_SLAB + fb0[j]);
@@ -632,7 +560,7 @@ __global__ __launch_bounds__(512) void gemm_h2w_kernel(H2Params p) {
             // mid: every request of this wave for D_{j+1} has landed; after the barrier every wave's have, and every wave is past its last
             // fragment read of D_j
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            h2_barrier();
+            dma_barrier();
             if (j + 2 < nd) dma_a(b0);                         // the A half of D_{j+2} into D_j's buffer
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -835,7 +763,7 @@ extern "C" int cham_split2h(const float* X, int R, int Cc, int ld, void* dst, lo
 extern "C" int cham_h2b_block_elements(void) { return H2B_BLOCK; }
 
 // launch counters: [0] NT launches, [1] TN launches, [2] NT launches on the 64-byte-piece kernel, [3] NT launches with a tile-blocked A,
-// [4] TN launches with a tile-blocked operand, [6] epilogue and [7] K-splits of the last launch
+// [4] TN launches with a tile-blocked operand, [5] NT launches with group sums, [6] epilogue and [7] K-splits of the last launch
 static long long g_h2_launches[8];
 extern "C" void cham_gemm_h2_launch_counts(long long* out8, int reset) {
     for (int i = 0; i < 8; ++i) { if (out8) out8[i] = g_h2_launches[i]; if (reset) g_h2_launches[i] = 0; }
@@ -845,31 +773,16 @@ extern "C" void cham_gemm_h2_launch_counts(long long* out8, int reset) {
 static int g_h2_nt_wide = 1;
 extern "C" int cham_gemm_h2_set_nt_wide(int on) { const int was = g_h2_nt_wide; g_h2_nt_wide = on ? 1 : 0; return was; }
 
-template <int EPI, bool ABLK>
-static int h2w_launch_l(H2Params& p, hipStream_t st) {
-    g_h2_launches[6] = EPI; g_h2_launches[7] = 1; ++g_h2_launches[2];
-    if (ABLK) ++g_h2_launches[3];
-    constexpr int smem = 2 * H2W_BUF;
-    auto k = gemm_h2w_kernel<EPI, ABLK>;
-    CHAM_SET_DYNAMIC_LDS(k, smem);
-    hipLaunchKernelGGL(k, dim3(p.nbm * p.nbn, 1, 1), dim3(512), smem, st, p);
-    CHAM_CHECK_LAUNCH();
-    return CHAM_OK;
+constexpr int H2_SMEM = H2_RING * H2_STAGE, H2W_SMEM = 2 * H2W_BUF;
+template <int EPI>
+static int h2w_launch(const H2Params& p, hipStream_t st) {
+    ++g_h2_launches[2];
+    if (p.a_tiles > 0) { ++g_h2_launches[3]; return dma_launch<gemm_h2w_kernel<EPI, true>, H2W_SMEM, EPI>(p, 1, g_h2_launches, st); }
+    return dma_launch<gemm_h2w_kernel<EPI, false>, H2W_SMEM, EPI>(p, 1, g_h2_launches, st);
 }
 template <int EPI>
-static int h2w_launch(H2Params& p, hipStream_t st) {
-    return p.a_tiles > 0 ? h2w_launch_l<EPI, true>(p, st) : h2w_launch_l<EPI, false>(p, st);
-}
-
-template <bool TN, int EPI>
-static int h2_launch(H2Params& p, hipStream_t st) {
-    g_h2_launches[6] = EPI; g_h2_launches[7] = p.splits;
-    constexpr int smem = H2_RING * H2_STAGE;
-    auto k = gemm_h2_kernel<TN, EPI>;
-    CHAM_SET_DYNAMIC_LDS(k, smem);
-    hipLaunchKernelGGL(k, dim3(p.nbm * p.nbn, p.splits, 1), dim3(512), smem, st, p);
-    CHAM_CHECK_LAUNCH();
-    return CHAM_OK;
+static int h2_launch_nt(const H2Params& p, bool wide, hipStream_t st) {
+    return wide ? h2w_launch<EPI>(p, st) : dma_launch<gemm_h2_kernel<false, EPI>, H2_SMEM, EPI>(p, 1, g_h2_launches, st);
 }
 // C[M,N] = epi((sum of the three plane products) / (s_a s_b)) - see the header.  A, B: plane 0 (fp16 h plane), the l plane
 // `*_plane_stride` elements further; a_scale / b_scale: the operands' H2Scale records (device memory, written by the kernels above).
@@ -891,7 +804,8 @@ static int h2_run(const void* A, long long a_plane_stride, int lda, const float*
                   int ldb, const float* b_scale, int tn, float* C, int ldc, int M, int N, int K, const float* bias, int act,
                   const void* dref_h, int ldr, int dact, int accumulate, float* workspace, size_t workspace_bytes, int splits_hint,
                   int a_tiles, int b_tiles, int dref_blocked, int group_rows, float* groupsum, size_t groupsum_bytes, void* stream) {
-    if (!A || !B || !C || !a_scale || !b_scale || M <= 0 || N <= 0 || K <= 0 || a_tiles < 0 || b_tiles < 0) return -CHAM_ERR_ARG;
+    const dma_plan::Args a = {A, B, C, a_plane_stride, b_plane_stride, lda, ldb, ldc, tn, M, N, K, bias, act, dref_h, ldr, dact, accumulate};
+    if (dma_plan::check_args(a, 16, false) != CHAM_OK || !a_scale || !b_scale || a_tiles < 0 || b_tiles < 0) return -CHAM_ERR_ARG;
     if (groupsum && (tn || !dref_h || group_rows < 32 || groupsum_bytes < cham_gemm_h2_groupsum_bytes(M, N, group_rows) || ((uintptr_t)groupsum & 15)))
         return -CHAM_ERR_ARG;
     {   // tile-blocked operands: whole column blocks, enough row tiles, planes that do not overlap
@@ -901,70 +815,34 @@ static int h2_run(const void* A, long long a_plane_stride, int lda, const float*
         if (!tn && (b_tiles || (a_tiles && (lda != K || (K & 31) || !g_h2_nt_wide)))) return -CHAM_ERR_ARG;
         if (dref_blocked && (!dref_h || (ldr & 31) || tn)) return -CHAM_ERR_ARG;      // (the caller allocates ceil(M / 256) row tiles of it)
     }
-    if ((lda & 7) || (ldb & 7) || (a_plane_stride & 7) || (b_plane_stride & 7) || (N & 3) || (ldc & 3)) return -CHAM_ERR_ARG;
-    if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return -CHAM_ERR_ARG;
-    if ((size_t)ldc * 4 * 256 >= WINDOW_BYTES || (size_t)ldr * 2 * 256 >= WINDOW_BYTES) return -CHAM_ERR_ARG;
-    if (lda < (tn ? M : K) || ldb < (tn ? N : K) || ldc < N || (dref_h && ldr < N)) return -CHAM_ERR_ARG;      // leading dimension < the extent it strides over
     H2Params p;
     p.A = reinterpret_cast<const _Float16*>(A); p.B = reinterpret_cast<const _Float16*>(B); p.a_ps = a_plane_stride; p.b_ps = b_plane_stride;
     p.lda = lda; p.ldb = ldb; p.sa = a_scale; p.sb = b_scale; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.bias = bias;
     p.dref = reinterpret_cast<const unsigned short*>(dref_h); p.ldr = ldr; p.partial = workspace; p.xcd_split = 0; p.accumulate = 0;
+    p.kchunk = K; p.splits = 1;
     p.nbm = (M + 255) / 256; p.nbn = (N + 255) / 256;
     p.a_tiles = a_tiles; p.b_tiles = b_tiles; p.r_blk = dref_blocked ? 1 : 0;
     p.gsum = groupsum; p.ggrp = group_rows; p.gsk = groupsum ? 127 / group_rows + 2 : 0;
     hipStream_t st = (hipStream_t)stream;
     if (!tn) {
-        if ((K & 15) || accumulate) return -CHAM_ERR_ARG;
-        if ((size_t)256 * lda * 2 >= (1ull << 31) || (size_t)256 * ldb * 2 >= (1ull << 31)) return -CHAM_ERR_ARG;
-        p.kchunk = K; p.splits = 1;
-        if (dref_h && (bias || act != ACT_NONE || dact != ACT_LEAKY)) return -CHAM_ERR_ARG;
-        if (act != ACT_NONE && !(bias && act == ACT_TANH)) return -CHAM_ERR_ARG;
+        const int epi = dma_plan::nt_epilogue(bias != nullptr, act, dref_h != nullptr, dact, true);
+        if (epi < 0) return -CHAM_ERR_ARG;
         ++g_h2_launches[0];
         if (groupsum) ++g_h2_launches[5];
-        if (g_h2_nt_wide && (K & 31) == 0) {
-            if (dref_h) return h2w_launch<3>(p, st);
-            if (bias) return act == ACT_TANH ? h2w_launch<2>(p, st) : h2w_launch<5>(p, st);
-            return h2w_launch<0>(p, st);
+        const bool wide = g_h2_nt_wide && (K & 31) == 0;
+        switch (epi) {
+            case 3: return h2_launch_nt<3>(p, wide, st);
+            case 2: return h2_launch_nt<2>(p, wide, st);
+            case 5: return h2_launch_nt<5>(p, wide, st);
+            default: return h2_launch_nt<0>(p, wide, st);
         }
-        if (dref_h) return h2_launch<false, 3>(p, st);
-        if (bias) return act == ACT_TANH ? h2_launch<false, 2>(p, st) : h2_launch<false, 5>(p, st);
-        return h2_launch<false, 0>(p, st);
     }
-    if ((M & 255) || (N & 255) || bias || act != ACT_NONE || dref_h) return -CHAM_ERR_ARG;
-    if ((size_t)16 * lda * 2 >= (1ull << 31) || (size_t)16 * ldb * 2 >= (1ull << 31)) return -CHAM_ERR_ARG;
-    const long tiles = (long)p.nbm * p.nbn;
-    int splits = 1;
-    if (splits_hint != 1 && workspace) {
-        long want = splits_hint > 1 ? splits_hint : (tiles >= 192 ? 1 : (256 + tiles - 1) / tiles);      // one workgroup per CU
-        const long maxk = (K + 511) / 512;
-        if (want > maxk) want = maxk;
-        const long maxw = (long)(workspace_bytes / ((size_t)M * N * sizeof(float)));
-        if (want > maxw) want = maxw;
-        if (splits_hint <= 0 && want >= 8) want = want / 8 * 8;      // (an explicit count is taken as given)
-        if (want > 1) splits = (int)want;
-    }
-    int kchunk = (K + splits - 1) / splits;
-    kchunk = ((kchunk + 15) / 16) * 16;
-    p.kchunk = kchunk;
-    p.splits = (K + kchunk - 1) / kchunk;
-    if ((size_t)kchunk * (lda > ldb ? lda : ldb) * 2 >= 0xFFFFFFF0ull) return -CHAM_ERR_ARG;
-    if ((a_tiles || b_tiles) && ((size_t)kchunk + 512 + 64) * (size_t)(lda > ldb ? lda : ldb) * 2 >= 0xFFFFFFF0ull) return -CHAM_ERR_ARG;      // offsets from kbeg's row tile
+    dma_plan::SplitPlan plan;
+    if (dma_plan::plan_tn_splits(M, N, K, lda, ldb, workspace != nullptr, workspace_bytes, splits_hint, 16, 512, plan) != CHAM_OK) return -CHAM_ERR_ARG;
+    if ((a_tiles || b_tiles) && ((size_t)plan.kchunk + 512 + 64) * (size_t)(lda > ldb ? lda : ldb) * 2 >= 0xFFFFFFF0ull) return -CHAM_ERR_ARG;      // offsets from kbeg's row tile
     ++g_h2_launches[1];
     if (a_tiles || b_tiles) ++g_h2_launches[4];
-    if (p.splits > 1) {
-        p.xcd_split = (p.splits % 8 == 0) ? 1 : 0;
-        const int rc = h2_launch<true, 6>(p, st);
-        if (rc != CHAM_OK) return rc;
-        GemmParams g;
-        g.A = nullptr; g.B = nullptr; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = 0; g.ldb = 0; g.ldc = ldc; g.bias = nullptr; g.act = ACT_NONE;
-        g.dref = nullptr; g.ldr = 0; g.dact = ACT_NONE; g.rs = nullptr; g.ldrs = 0; g.rs_div = 1; g.accumulate = accumulate;
-        g.kchunk = kchunk; g.splits = p.splits; g.partial = workspace; g.nbm = p.nbm; g.nbn = p.nbn; g.xcd_split = p.xcd_split;
-        launch_splitk_reduce(g, st);
-        CHAM_CHECK_LAUNCH();
-        return CHAM_OK;
-    }
-    p.accumulate = accumulate;
-    return h2_launch<true, 0>(p, st);
+    return dma_launch_tn<gemm_h2_kernel<true, 6>, gemm_h2_kernel<true, 0>, H2_SMEM>(p, plan, accumulate, g_h2_launches, st);
 }
 
 extern "C" int cham_gemm_h2b(const void* A, long long a_plane_stride, int lda, const float* a_scale, const void* B, long long b_plane_stride,

@@ -30,11 +30,8 @@
 //   A DMA has 1.5 steps (~4 600 cycles at two waves per SIMD) to land.  Ragged rows / K tails rely on the buffer descriptor's range
 //   check (one descriptor per plane: out-of-range pieces arrive as zeros).
 // Epilogues: plain, + bias -> tanh (CAR forward), x leaky'(h plane of the saved activation) (CAR dgrad), split-K partial (wgrad).
-#include "gemm_shared.h"
+#include "gemm_dma.h"
 #include <type_traits>
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct P3Params {
     const __bf16* A; const __bf16* B;          // plane 0 of each operand
@@ -51,13 +48,6 @@ struct P3Params {
 #define P3_SLAB 8192
 #define P3_STAGE (6 * P3_SLAB)
 #define P3_RING 3
-
-__device__ __forceinline__ u32x4 p3_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    u32x4 r;
-    r.x = (unsigned)a; r.y = (unsigned)(a >> 32) & 0xFFFFu; r.z = bytes; r.w = 0x00020000u;
-    return r;
-}
 
 // six LDS-DMA requests of one stage: 16 bytes per lane, LDS destination = M0 + lane * 16 (wave-uniform), source = descriptor base
 // + voffset (per lane; the K advance is part of it, so that the descriptor's range check - which ignores an SGPR offset - sees it).
@@ -80,31 +70,6 @@ __device__ __forceinline__ void p3_dma_stage(unsigned lds0, unsigned va, unsigne
         : "s"(lds0), "s"(l1), "s"(l2), "s"(l3), "s"(l4), "s"(l5), "v"(va), "v"(vb), "s"(ra0), "s"(ra1), "s"(ra2), "s"(rb0), "s"(rb1),
           "s"(rb2)
         : "memory");
-}
-
-template <bool TN>
-__device__ __forceinline__ bf16x8 p3_frag(const unsigned char* __restrict__ s) {
-    if constexpr (!TN) {
-        return *reinterpret_cast<const bf16x8*>(s);
-    } else {
-        typedef __attribute__((address_space(3))) s16x4 lds_s4;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(s));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(s + 4 * 512));
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        s16x8 v;
-        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-        return __builtin_bit_cast(bf16x8, v);
-    }
-}
-
-// LDS-only barrier (gemm_x3.hip): builtins so that the wait-count pass sees the drain; vmcnt is handled by hand (the DMA requests are
-// invisible to the compiler).
-__device__ __forceinline__ void p3_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 // epilogue of the plane kernels: acc[i][j][e] = element (row wm0 + 32 i + (e & 3) + 8 (e >> 2) + 4 kl, column wn0 + 32 j + fl) of the tile at (m0, n0)
@@ -141,11 +106,7 @@ __device__ __forceinline__ void p3_epilogue(const P3Params& p, floatx16 (&acc)[T
                 }
             }
     } else {
-        GemmParams g;
-        g.A = nullptr; g.B = nullptr; g.C = p.C; g.M = p.M; g.N = p.N; g.K = p.K; g.lda = 0; g.ldb = 0; g.ldc = p.ldc;
-        g.bias = p.bias; g.act = ACT_NONE; g.dref = nullptr; g.ldr = 0; g.dact = ACT_NONE; g.rs = nullptr; g.ldrs = 0; g.rs_div = 1;
-        g.accumulate = p.accumulate; g.kchunk = p.kchunk; g.splits = p.splits; g.partial = p.partial; g.nbm = p.nbm; g.nbn = p.nbn; g.xcd_split = p.xcd_split;
-        gemm_epilogue<EPI, TM, TNN>(g, acc, m0, n0, wm0, wn0, split, kl, fl);
+        gemm_epilogue<EPI, TM, TNN>(epilogue_params(p, p.bias), acc, m0, n0, wm0, wn0, split, kl, fl);
     }
 }
 
@@ -158,20 +119,8 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
     constexpr int BM = 256, BN = 256, BK = 16, TM = 4, TNN = 2;
     extern __shared__ __attribute__((aligned(1024))) unsigned char p3_smem[];
 
-    const int nwg = p.nbm * p.nbn;
     int tile_m, tile_n, split;
-    if (p.xcd_split) {                                 // one K-split per XCD (gemm.hip): every K panel is fetched from HBM once
-        const int lin = blockIdx.x + gridDim.x * blockIdx.y, slot = lin >> 3;
-        split = (lin & 7) + 8 * (slot / nwg);
-        const int t = slot % nwg;
-        tile_m = t / p.nbn; tile_n = t % p.nbn;
-    } else {                                           // XCD-aware bijective swizzle: the column tiles of an A panel share an L2
-        const int id = blockIdx.x;
-        const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-        const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-        tile_m = swz / p.nbn; tile_n = swz % p.nbn;
-        split = blockIdx.y;
-    }
+    gemm_tile_map(p, tile_m, tile_n, split);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int kbeg = split * p.kchunk;
     const int kend = min(p.K, kbeg + p.kchunk);
@@ -189,8 +138,8 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
         const size_t abytes = aall > koff ? aall - koff : 0, bbytes = ball > koff ? ball - koff : 0;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            ra[q] = p3_rsrc(p.A + q * p.a_ps + (size_t)m0 * p.lda + kbeg, (unsigned)min(abytes, (size_t)0xFFFFFFF0u));
-            rb[q] = p3_rsrc(p.B + q * p.b_ps + (size_t)n0 * p.ldb + kbeg, (unsigned)min(bbytes, (size_t)0xFFFFFFF0u));
+            ra[q] = dma_rsrc(p.A + q * p.a_ps + (size_t)m0 * p.lda + kbeg, (unsigned)min(abytes, (size_t)0xFFFFFFF0u));
+            rb[q] = dma_rsrc(p.B + q * p.b_ps + (size_t)n0 * p.ldb + kbeg, (unsigned)min(bbytes, (size_t)0xFFFFFFF0u));
         }
         // lane l of wave w fills LDS piece (row 32 w + l / 2, half l & 1); that piece holds source half (l & 1) ^ bit 3 of the row
         const int row = 32 * wave + (lane >> 1), half = (lane & 1) ^ ((lane >> 4) & 1);
@@ -201,8 +150,8 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
         const size_t abytes = (size_t)max(kend - kbeg, 0) * p.lda * 2, bbytes = (size_t)max(kend - kbeg, 0) * p.ldb * 2;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {      // (M, N multiples of 256: the m / n extent of a tile never leaves its k-row)
-            ra[q] = p3_rsrc(p.A + q * p.a_ps + (size_t)kbeg * p.lda + m0, (unsigned)min(abytes - (size_t)m0 * 2, (size_t)0xFFFFFFF0u));
-            rb[q] = p3_rsrc(p.B + q * p.b_ps + (size_t)kbeg * p.ldb + n0, (unsigned)min(bbytes - (size_t)n0 * 2, (size_t)0xFFFFFFF0u));
+            ra[q] = dma_rsrc(p.A + q * p.a_ps + (size_t)kbeg * p.lda + m0, (unsigned)min(abytes - (size_t)m0 * 2, (size_t)0xFFFFFFF0u));
+            rb[q] = dma_rsrc(p.B + q * p.b_ps + (size_t)kbeg * p.ldb + n0, (unsigned)min(bbytes - (size_t)n0 * 2, (size_t)0xFFFFFFF0u));
         }
         // lane l of wave w fills LDS piece (k-row 2 w + l / 32, piece l & 31); its 64-byte group index is XOR-ed with k & 3
         const int k = 2 * wave + (lane >> 5), jp = lane & 31, j = ((((jp >> 2) ^ (k & 3)) << 2) | (jp & 3));
@@ -248,17 +197,17 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
         p3_dma_stage(lds_base + P3_STAGE + wave_off, va, vb, ra[0], ra[1], ra[2], rb[0], rb[1], rb[2]);
         va += stepa; vb += stepb;
         asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        p3_barrier();
+        dma_barrier();
         {   // early fragments of stage 0
             const unsigned char* S = p3_smem;
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) BH[j] = p3_frag<TN>(S + 3 * P3_SLAB + fb[j]);
+            for (int j = 0; j < TNN; ++j) BH[j] = dma_frag<bf16x8, TN>(S + 3 * P3_SLAB + fb[j]);
 #pragma unroll
-            for (int i = 0; i < TM; ++i) AL[i] = p3_frag<TN>(S + 2 * P3_SLAB + fa[i]);
+            for (int i = 0; i < TM; ++i) AL[i] = dma_frag<bf16x8, TN>(S + 2 * P3_SLAB + fa[i]);
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) BL[j] = p3_frag<TN>(S + 5 * P3_SLAB + fb[j]);
+            for (int j = 0; j < TNN; ++j) BL[j] = dma_frag<bf16x8, TN>(S + 5 * P3_SLAB + fb[j]);
 #pragma unroll
-            for (int i = 0; i < TM; ++i) AM[i] = p3_frag<TN>(S + 1 * P3_SLAB + fa[i]);
+            for (int i = 0; i < TM; ++i) AM[i] = dma_frag<bf16x8, TN>(S + 1 * P3_SLAB + fa[i]);
         }
         int cur = 0;                                    // slot of stage i
         for (int i = 0; i < nk; ++i) {
@@ -273,9 +222,9 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
             __builtin_amdgcn_sched_barrier(0);
             // P0: A_l x B_h; late fragments of this stage
 #pragma unroll
-            for (int ii = 0; ii < TM; ++ii) AH[ii] = p3_frag<TN>(Sc + 0 * P3_SLAB + fa[ii]);
+            for (int ii = 0; ii < TM; ++ii) AH[ii] = dma_frag<bf16x8, TN>(Sc + 0 * P3_SLAB + fa[ii]);
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) BMf[j] = p3_frag<TN>(Sc + 4 * P3_SLAB + fb[j]);
+            for (int j = 0; j < TNN; ++j) BMf[j] = dma_frag<bf16x8, TN>(Sc + 4 * P3_SLAB + fb[j]);
 #pragma unroll
             for (int ii = 0; ii < TM; ++ii)
 #pragma unroll
@@ -296,12 +245,12 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
             // mid: this wave's requests for stage i + 1 have landed (the six of stage i + 2 stay in flight); after the barrier every
             // wave's have
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            p3_barrier();
+            dma_barrier();
             // P3: A_h x B_l; early fragments of stage i + 1 into the registers that are dead
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) BH[j] = p3_frag<TN>(Sn + 3 * P3_SLAB + fb[j]);
+            for (int j = 0; j < TNN; ++j) BH[j] = dma_frag<bf16x8, TN>(Sn + 3 * P3_SLAB + fb[j]);
 #pragma unroll
-            for (int ii = 0; ii < TM; ++ii) AL[ii] = p3_frag<TN>(Sn + 2 * P3_SLAB + fa[ii]);
+            for (int ii = 0; ii < TM; ++ii) AL[ii] = dma_frag<bf16x8, TN>(Sn + 2 * P3_SLAB + fa[ii]);
 #pragma unroll
             for (int ii = 0; ii < TM; ++ii)
 #pragma unroll
@@ -309,7 +258,7 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
             __builtin_amdgcn_sched_barrier(0);
             // P4: A_m x B_m
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) BL[j] = p3_frag<TN>(Sn + 5 * P3_SLAB + fb[j]);
+            for (int j = 0; j < TNN; ++j) BL[j] = dma_frag<bf16x8, TN>(Sn + 5 * P3_SLAB + fb[j]);
 #pragma unroll
             for (int ii = 0; ii < TM; ++ii)
 #pragma unroll
@@ -317,7 +266,7 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
             __builtin_amdgcn_sched_barrier(0);
             // P5: A_h x B_m
 #pragma unroll
-            for (int ii = 0; ii < TM; ++ii) AM[ii] = p3_frag<TN>(Sn + 1 * P3_SLAB + fa[ii]);
+            for (int ii = 0; ii < TM; ++ii) AM[ii] = dma_frag<bf16x8, TN>(Sn + 1 * P3_SLAB + fa[ii]);
 #pragma unroll
             for (int ii = 0; ii < TM; ++ii)
 #pragma unroll
@@ -347,14 +296,6 @@ __global__ __launch_bounds__(512) void gemm_p3_kernel(P3Params p) {
 //   NT runs the MFMAs with swapped operands (accumulator = C^T: a lane owns four consecutive output columns of its row), so the
 //   bf16 epilogues load / store 8 bytes per access (as gemm_b16.hip); TN keeps the shared split-K partial epilogue.
 // EPI: NT 12 = + bias -> tanh -> bf16, 13 = x leaky'(saved bf16 activation) -> bf16, 10 = plain -> bf16;  TN 6 = split-K partial, 0 = fp32.
-__device__ __forceinline__ float b1_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float b1_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-__device__ __forceinline__ unsigned b1_pack(float a, float b) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v; v[0] = (__bf16)a; v[1] = (__bf16)b;           // v_cvt_pk_bf16_f32 (round to nearest even)
-    return __builtin_bit_cast(unsigned, v);
-}
-
 // The NT epilogue of the bf16-resident kernels (accumulators of SWAPPED products: acc[i][j][e] = row m0 + wm0 + 32 i + fl, column n0 + wn0 +
 // 32 j + 8 (e >> 2) + 4 kl + (e & 3)); shared by gemm_b1_kernel<false, .> and gemm_b1w_kernel.  Needs the kernel's 128 KB of dynamic LDS.
 template <int EPI>
@@ -380,7 +321,7 @@ __device__ __forceinline__ void b1_nt_epilogue(const P3Params& p, floatx16 (&acc
         // column group: 32 different bank pairs) - reads it back 16 bytes per lane (8 lanes = one whole 128-byte row segment; two rows per 16
         // lanes = all 64 banks) and stores / loads global memory in whole lines: 16 b128 accesses per lane instead of 32 b64.
         // The dgrad (EPI 13) works in two halves of 64 rows: [saved activation | outputs] share the wave's 16 KB.
-        p3_barrier();                 // every wave is past its last fragment read; no DMA in flight (vmcnt(0) above): the ring is free
+        dma_barrier();                 // every wave is past its last fragment read; no DMA in flight (vmcnt(0) above): the ring is free
         if (limM >= wm0 + 128 && limN >= wn0 + 64) {          // wave-uniform
             unsigned char* Rg = p3_smem + (unsigned)wave * 16384u;
             const unsigned lr = (unsigned)(lane >> 3), ls = (unsigned)(lane & 7);
@@ -402,7 +343,7 @@ __device__ __forceinline__ void b1_nt_epilogue(const P3Params& p, floatx16 (&acc
                                 v[2] = cham_tanhf(v[2] + __uint_as_float(bv.z)); v[3] = cham_tanhf(v[3] + __uint_as_float(bv.w));
                             }
                             u32x2 w;
-                            w.x = b1_pack(v[0], v[1]); w.y = b1_pack(v[2], v[3]);
+                            w.x = pack_bf2(v[0], v[1]); w.y = pack_bf2(v[2], v[3]);
                             *reinterpret_cast<u32x2*>(Rg + slot_off((unsigned)(32 * i + fl), (unsigned)(4 * j + q), (unsigned)kl)) = w;
                         }
                     }
@@ -436,10 +377,10 @@ __device__ __forceinline__ void b1_nt_epilogue(const P3Params& p, floatx16 (&acc
                                 const unsigned off = slot_off((unsigned)(32 * ih + fl), (unsigned)(4 * j + q), (unsigned)kl);
                                 const u32x2 y = *reinterpret_cast<const u32x2*>(Dg + off);
                                 float v[4] = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                                v[0] *= b1_lo(y.x) > 0.f ? 1.f : 0.2f; v[1] *= b1_hi(y.x) > 0.f ? 1.f : 0.2f;
-                                v[2] *= b1_lo(y.y) > 0.f ? 1.f : 0.2f; v[3] *= b1_hi(y.y) > 0.f ? 1.f : 0.2f;
+                                v[0] *= bf_lo(y.x) > 0.f ? 1.f : 0.2f; v[1] *= bf_hi(y.x) > 0.f ? 1.f : 0.2f;
+                                v[2] *= bf_lo(y.y) > 0.f ? 1.f : 0.2f; v[3] *= bf_hi(y.y) > 0.f ? 1.f : 0.2f;
                                 u32x2 w;
-                                w.x = b1_pack(v[0], v[1]); w.y = b1_pack(v[2], v[3]);
+                                w.x = pack_bf2(v[0], v[1]); w.y = pack_bf2(v[2], v[3]);
                                 *reinterpret_cast<u32x2*>(Og + off) = w;
                             }
 #pragma unroll
@@ -472,11 +413,11 @@ __device__ __forceinline__ void b1_nt_epilogue(const P3Params& p, floatx16 (&acc
                     }
                     if constexpr (EPI == 13) {
                         const u32x2 y = __builtin_amdgcn_raw_buffer_load_b64(dw, ok ? ((unsigned)m * (unsigned)p.ldr + (unsigned)n) * 2u : OOB_OFF, 0, 0);
-                        v[0] *= b1_lo(y.x) > 0.f ? 1.f : 0.2f; v[1] *= b1_hi(y.x) > 0.f ? 1.f : 0.2f;
-                        v[2] *= b1_lo(y.y) > 0.f ? 1.f : 0.2f; v[3] *= b1_hi(y.y) > 0.f ? 1.f : 0.2f;
+                        v[0] *= bf_lo(y.x) > 0.f ? 1.f : 0.2f; v[1] *= bf_hi(y.x) > 0.f ? 1.f : 0.2f;
+                        v[2] *= bf_lo(y.y) > 0.f ? 1.f : 0.2f; v[3] *= bf_hi(y.y) > 0.f ? 1.f : 0.2f;
                     }
                     u32x2 w;
-                    w.x = b1_pack(v[0], v[1]); w.y = b1_pack(v[2], v[3]);
+                    w.x = pack_bf2(v[0], v[1]); w.y = pack_bf2(v[2], v[3]);
                     __builtin_amdgcn_raw_buffer_store_b64(w, cw, ok ? ((unsigned)m * (unsigned)p.ldc + (unsigned)n) * 2u : OOB_OFF, 0, 0);
                 }
         }
@@ -489,6 +430,8 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(P3Params p) {
     constexpr bool SWAP = !TN;
     extern __shared__ __attribute__((aligned(1024))) unsigned char p3_smem[];
 
+    // (gemm_shared.h's gemm_tile_map and gemm_dma.h's epilogue_params, written out: with either helper the TN instances of THIS kernel come
+    // out with another register allocation - scripts/kernel_isa_diff.py, profiles/gemm_dma_core_notes.md)
     const int nwg = p.nbm * p.nbn;
     int tile_m, tile_n, split;
     if (p.xcd_split) {
@@ -518,8 +461,8 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(P3Params p) {
         const size_t abytes = (size_t)max(p.M - m0, 0) * p.lda * 2, bbytes = (size_t)max(p.N - n0, 0) * p.ldb * 2;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            ra[q] = p3_rsrc(p.A + (size_t)m0 * p.lda + kbeg + 16 * q, (unsigned)min(abytes > 32u * q ? abytes - 32u * q : (size_t)0, (size_t)0xFFFFFFF0u));
-            rb[q] = p3_rsrc(p.B + (size_t)n0 * p.ldb + kbeg + 16 * q, (unsigned)min(bbytes > 32u * q ? bbytes - 32u * q : (size_t)0, (size_t)0xFFFFFFF0u));
+            ra[q] = dma_rsrc(p.A + (size_t)m0 * p.lda + kbeg + 16 * q, (unsigned)min(abytes > 32u * q ? abytes - 32u * q : (size_t)0, (size_t)0xFFFFFFF0u));
+            rb[q] = dma_rsrc(p.B + (size_t)n0 * p.ldb + kbeg + 16 * q, (unsigned)min(bbytes > 32u * q ? bbytes - 32u * q : (size_t)0, (size_t)0xFFFFFFF0u));
         }
         const int row = 32 * wave + (lane >> 1), half = (lane & 1) ^ ((lane >> 4) & 1);
         va = ((unsigned)row * (unsigned)p.lda + 8u * half) * 2u;
@@ -530,8 +473,8 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(P3Params p) {
         for (int q = 0; q < 3; ++q) {
             const size_t rows = (size_t)max(klen - 16 * q, 0);
             const size_t abytes = rows * p.lda * 2, bbytes = rows * p.ldb * 2;
-            ra[q] = p3_rsrc(p.A + (size_t)(kbeg + 16 * q) * p.lda + m0, (unsigned)min(abytes > (size_t)m0 * 2 ? abytes - (size_t)m0 * 2 : (size_t)0, (size_t)0xFFFFFFF0u));
-            rb[q] = p3_rsrc(p.B + (size_t)(kbeg + 16 * q) * p.ldb + n0, (unsigned)min(bbytes > (size_t)n0 * 2 ? bbytes - (size_t)n0 * 2 : (size_t)0, (size_t)0xFFFFFFF0u));
+            ra[q] = dma_rsrc(p.A + (size_t)(kbeg + 16 * q) * p.lda + m0, (unsigned)min(abytes > (size_t)m0 * 2 ? abytes - (size_t)m0 * 2 : (size_t)0, (size_t)0xFFFFFFF0u));
+            rb[q] = dma_rsrc(p.B + (size_t)(kbeg + 16 * q) * p.ldb + n0, (unsigned)min(bbytes > (size_t)n0 * 2 ? bbytes - (size_t)n0 * 2 : (size_t)0, (size_t)0xFFFFFFF0u));
         }
         const int k = 2 * wave + (lane >> 5), jp = lane & 31, j = ((((jp >> 2) ^ (k & 3)) << 2) | (jp & 3));
         va = ((unsigned)k * (unsigned)p.lda + 8u * j) * 2u;
@@ -600,11 +543,11 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(P3Params p) {
         dma(0, 0u);
         dma(1, 1u);
         asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        p3_barrier();
+        dma_barrier();
 #pragma unroll
-        for (int ii = 0; ii < TM; ++ii) A0[ii] = p3_frag<TN>(p3_smem + 0 * P3_SLAB + fa[ii]);
+        for (int ii = 0; ii < TM; ++ii) A0[ii] = dma_frag<bf16x8, TN>(p3_smem + 0 * P3_SLAB + fa[ii]);
 #pragma unroll
-        for (int j = 0; j < TNN; ++j) B0[j] = p3_frag<TN>(p3_smem + 3 * P3_SLAB + fb[j]);
+        for (int j = 0; j < TNN; ++j) B0[j] = dma_frag<bf16x8, TN>(p3_smem + 3 * P3_SLAB + fb[j]);
         int cur = 0;
         for (int i = 0; i < nk; ++i) {
             const int nxt = cur == P3_RING - 1 ? 0 : cur + 1, nx2 = nxt == P3_RING - 1 ? 0 : nxt + 1;
@@ -614,21 +557,21 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(P3Params p) {
             dma(i + 2, (unsigned)nx2);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int ii = 0; ii < TM; ++ii) A1[ii] = p3_frag<TN>(Sc + 1 * P3_SLAB + fa[ii]);
+            for (int ii = 0; ii < TM; ++ii) A1[ii] = dma_frag<bf16x8, TN>(Sc + 1 * P3_SLAB + fa[ii]);
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) B1[j] = p3_frag<TN>(Sc + 4 * P3_SLAB + fb[j]);
+            for (int j = 0; j < TNN; ++j) B1[j] = dma_frag<bf16x8, TN>(Sc + 4 * P3_SLAB + fb[j]);
             mma(A0, B0);
 #pragma unroll
-            for (int ii = 0; ii < TM; ++ii) A2[ii] = p3_frag<TN>(Sc + 2 * P3_SLAB + fa[ii]);
+            for (int ii = 0; ii < TM; ++ii) A2[ii] = dma_frag<bf16x8, TN>(Sc + 2 * P3_SLAB + fa[ii]);
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) B2[j] = p3_frag<TN>(Sc + 5 * P3_SLAB + fb[j]);
+            for (int j = 0; j < TNN; ++j) B2[j] = dma_frag<bf16x8, TN>(Sc + 5 * P3_SLAB + fb[j]);
             mma(A1, B1);
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            p3_barrier();
+            dma_barrier();
 #pragma unroll
-            for (int ii = 0; ii < TM; ++ii) A0[ii] = p3_frag<TN>(Sn + 0 * P3_SLAB + fa[ii]);
+            for (int ii = 0; ii < TM; ++ii) A0[ii] = dma_frag<bf16x8, TN>(Sn + 0 * P3_SLAB + fa[ii]);
 #pragma unroll
-            for (int j = 0; j < TNN; ++j) B0[j] = p3_frag<TN>(Sn + 3 * P3_SLAB + fb[j]);
+            for (int j = 0; j < TNN; ++j) B0[j] = dma_frag<bf16x8, TN>(Sn + 3 * P3_SLAB + fb[j]);
             mma(A2, B2);
             cur = nxt;
         }
@@ -667,34 +610,13 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(P3Params p) {
 #define B1W_SLAB 16384
 #define B1W_BUF (4 * B1W_SLAB)
 
-// four requests of one operand: the two 16-row halves of a wave's 32 rows, in the k 0..31 slab (descriptor r0) and the k 32..63 slab (r1 =
-// the same rows 64 bytes further)
-__device__ __forceinline__ void b1w_dma4(unsigned l0, unsigned l1, unsigned v0, unsigned v1, const u32x4& r0, const u32x4& r1) {
-    unsigned keep;
-    const unsigned l0b = l0 + 1024u, l1b = l1 + 1024u;
-    asm volatile(
-        "s_nop 4\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %7, 0 offen lds\n\t"
-        "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %7, 0 offen lds\n\t"
-        "s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %8, 0 offen lds\n\t"
-        "s_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %8, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "s"(l0), "s"(l0b), "s"(l1), "s"(l1b), "v"(v0), "v"(v1), "s"(r0), "s"(r1)
-        : "memory");
-}
-
 // EPI: 12 = + bias -> tanh -> bf16, 13 = x leaky'(saved bf16 activation) -> bf16, 10 = plain -> bf16
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_b1w_kernel(P3Params p) {
     constexpr int BM = 256, BN = 256, TM = 4, TNN = 2;
     extern __shared__ __attribute__((aligned(1024))) unsigned char p3_smem[];
-    const int nwg = p.nbm * p.nbn;
-    const int id = blockIdx.x;
-    const int q8 = nwg / 8, rr = nwg % 8, xcd = id % 8;       // XCD-aware bijective swizzle: the column tiles of an A panel share an L2
-    const int swz = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + id / 8;
-    const int tile_m = swz / p.nbn, tile_n = swz % p.nbn;
+    int tile_m, tile_n, split;
+    gemm_tile_map<false>(p, tile_m, tile_n, split);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int nd = p.K >> 6;                                   // 64-k buffers
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -705,10 +627,11 @@ __global__ __launch_bounds__(512) void gemm_b1w_kernel(P3Params p) {
     const size_t aall = (size_t)max(p.M - m0, 0) * p.lda * 2, ball = (size_t)max(p.N - n0, 0) * p.ldb * 2;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        ra[q] = p3_rsrc(p.A + (size_t)m0 * p.lda + 32 * q, (unsigned)min(aall > 64u * q ? aall - 64u * q : (size_t)0, (size_t)0xFFFFFFF0u));
-        rb[q] = p3_rsrc(p.B + (size_t)n0 * p.ldb + 32 * q, (unsigned)min(ball > 64u * q ? ball - 64u * q : (size_t)0, (size_t)0xFFFFFFF0u));
+        ra[q] = dma_rsrc(p.A + (size_t)m0 * p.lda + 32 * q, (unsigned)min(aall > 64u * q ? aall - 64u * q : (size_t)0, (size_t)0xFFFFFFF0u));
+        rb[q] = dma_rsrc(p.B + (size_t)n0 * p.ldb + 32 * q, (unsigned)min(ball > 64u * q ? ball - 64u * q : (size_t)0, (size_t)0xFFFFFFF0u));
     }
     // lane l of wave w, request half r: LDS piece (row 32 w + 16 r + l / 4, piece l & 3) <- source piece (l & 3) ^ ((row >> 2) & 3)
+    // (this map and the fragment offsets below: the text of gemm_h2w_kernel - see gemm_dma.h for why it is not a shared helper)
     const unsigned row = 32u * (unsigned)wave + (unsigned)(lane >> 2), sp = (unsigned)((lane & 3) ^ ((lane >> 4) & 3));
     unsigned va0 = (row * (unsigned)p.lda + 8u * sp) * 2u, va1 = va0 + 16u * (unsigned)p.lda * 2u;
     unsigned vb0 = (row * (unsigned)p.ldb + 8u * sp) * 2u, vb1 = vb0 + 16u * (unsigned)p.ldb * 2u;
@@ -751,11 +674,11 @@ __global__ __launch_bounds__(512) void gemm_b1w_kernel(P3Params p) {
         for (int j = 0; j < TNN; ++j) Y[j] = *reinterpret_cast<const bf16x8*>(S + (2 + slab) * B1W_SLAB + fb[j]);
     };
     auto dma_a = [&](unsigned buf) {
-        b1w_dma4(lds_base + buf + 0 * B1W_SLAB + wave_off, lds_base + buf + 1 * B1W_SLAB + wave_off, va0, va1, ra[0], ra[1]);
+        dma4(lds_base + buf + 0 * B1W_SLAB + wave_off, lds_base + buf + 1 * B1W_SLAB + wave_off, va0, va1, ra[0], ra[1]);
         va0 += 128u; va1 += 128u;
     };
     auto dma_b = [&](unsigned buf) {
-        b1w_dma4(lds_base + buf + 2 * B1W_SLAB + wave_off, lds_base + buf + 3 * B1W_SLAB + wave_off, vb0, vb1, rb[0], rb[1]);
+        dma4(lds_base + buf + 2 * B1W_SLAB + wave_off, lds_base + buf + 3 * B1W_SLAB + wave_off, vb0, vb1, rb[0], rb[1]);
         vb0 += 128u; vb1 += 128u;
     };
 
@@ -767,7 +690,7 @@ __global__ __launch_bounds__(512) void gemm_b1w_kernel(P3Params p) {
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        p3_barrier();
+        dma_barrier();
         rd(A0, B0, p3_smem, 0, fa0, fb0);                        // chunk 0 of D_0
         for (int j = 0; j < nd; ++j) {
             const unsigned b0 = (unsigned)(j & 1) * (unsigned)B1W_BUF, b1 = (unsigned)B1W_BUF - b0;
@@ -783,7 +706,7 @@ __global__ __launch_bounds__(512) void gemm_b1w_kernel(P3Params p) {
             rd(A1, B1, S0, 1, fa1, fb1);                         // chunk 3
             mma(A0, B0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // D_{j+1}: this wave's requests have landed; after the barrier every wave's have,
-            p3_barrier();                                         // and every wave is past its last fragment read of D_j
+            dma_barrier();                                         // and every wave is past its last fragment read of D_j
             if (j + 2 < nd) dma_a(b0);                           // the A slabs of D_{j+2} into D_j's buffer
             __builtin_amdgcn_sched_barrier(0);
             if (j + 1 < nd) rd(A0, B0, S1, 0, fa0, fb0);         // chunk 0 of D_{j+1}
@@ -820,21 +743,30 @@ extern "C" int cham_split3(const float* X, int R, int Cc, int ld, void* dst, lon
     return CHAM_OK;
 }
 
-// launch counters: [0] NT launches, [1] TN launches, [2] / [3] NT / TN launches of the one-plane bf16 form, [6] epilogue and [7] K-splits of the last launch
+// launch counters: [0] NT launches, [1] TN launches, [2] / [3] NT / TN launches of the one-plane bf16 form, [4] NT launches of that form on
+// the 64-byte-piece kernel, [6] epilogue and [7] K-splits of the last launch
 static long long g_p3_launches[8];
 extern "C" void cham_gemm_p3_launch_counts(long long* out8, int reset) {
     for (int i = 0; i < 8; ++i) { if (out8) out8[i] = g_p3_launches[i]; if (reset) g_p3_launches[i] = 0; }
 }
 
+constexpr int P3_SMEM = P3_RING * P3_STAGE, B1W_SMEM = 2 * B1W_BUF;
 template <bool TN, int EPI>
-static int p3_launch(P3Params& p, hipStream_t st) {
-    g_p3_launches[6] = EPI; g_p3_launches[7] = p.splits;
-    constexpr int smem = P3_RING * P3_STAGE;
-    auto k = gemm_p3_kernel<TN, EPI>;
-    CHAM_SET_DYNAMIC_LDS(k, smem);
-    hipLaunchKernelGGL(k, dim3(p.nbm * p.nbn, p.splits, 1), dim3(512), smem, st, p);
-    CHAM_CHECK_LAUNCH();
-    return CHAM_OK;
+static int p3_launch(const P3Params& p, hipStream_t st) { return dma_launch<gemm_p3_kernel<TN, EPI>, P3_SMEM, EPI>(p, p.splits, g_p3_launches, st); }
+template <bool TN, int EPI>
+static int b1_launch(const P3Params& p, hipStream_t st) { return dma_launch<gemm_b1_kernel<TN, EPI>, P3_SMEM, EPI>(p, p.splits, g_p3_launches, st); }
+template <int EPI>
+static int b1w_launch(const P3Params& p, hipStream_t st) { return dma_launch<gemm_b1w_kernel<EPI>, B1W_SMEM, EPI>(p, 1, g_p3_launches, st); }
+
+// the parameter block of a checked call: one K range, no accumulation (a TN plan changes both: dma_launch_tn)
+static P3Params p3_params(const dma_plan::Args& a, float* workspace) {
+    P3Params p;
+    p.A = reinterpret_cast<const __bf16*>(a.A); p.B = reinterpret_cast<const __bf16*>(a.B); p.a_ps = a.a_plane_stride; p.b_ps = a.b_plane_stride;
+    p.lda = a.lda; p.ldb = a.ldb; p.C = reinterpret_cast<float*>(const_cast<void*>(a.C)); p.ldc = a.ldc; p.M = a.M; p.N = a.N; p.K = a.K;
+    p.bias = reinterpret_cast<const float*>(a.bias); p.dref = reinterpret_cast<const __bf16*>(a.dref); p.ldr = a.ldr;
+    p.kchunk = a.K; p.splits = 1; p.partial = workspace; p.xcd_split = 0; p.accumulate = 0;
+    p.nbm = (a.M + 255) / 256; p.nbn = (a.N + 255) / 256;
+    return p;
 }
 
 // C[M,N] = epi(sum of six plane products) - see the header.  A, B: plane 0 (bf16), planes `*_plane_stride` elements apart.
@@ -846,66 +778,24 @@ static int p3_launch(P3Params& p, hipStream_t st) {
 extern "C" int cham_gemm_p3(const void* A, long long a_plane_stride, int lda, const void* B, long long b_plane_stride, int ldb, int tn,
                             float* C, int ldc, int M, int N, int K, const float* bias, int act, const void* dref_h, int ldr, int dact,
                             int accumulate, float* workspace, size_t workspace_bytes, int splits_hint, void* stream) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return -CHAM_ERR_ARG;
-    if ((lda & 7) || (ldb & 7) || (a_plane_stride & 7) || (b_plane_stride & 7) || (N & 3) || (ldc & 3)) return -CHAM_ERR_ARG;
-    if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return -CHAM_ERR_ARG;
-    if ((size_t)ldc * 4 * 256 >= WINDOW_BYTES || (size_t)ldr * 2 * 256 >= WINDOW_BYTES) return -CHAM_ERR_ARG;
-    if (lda < (tn ? M : K) || ldb < (tn ? N : K) || ldc < N || (dref_h && ldr < N)) return -CHAM_ERR_ARG;      // leading dimension < the extent it strides over
-    P3Params p;
-    p.A = reinterpret_cast<const __bf16*>(A); p.B = reinterpret_cast<const __bf16*>(B); p.a_ps = a_plane_stride; p.b_ps = b_plane_stride;
-    p.lda = lda; p.ldb = ldb; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.bias = bias;
-    p.dref = reinterpret_cast<const __bf16*>(dref_h); p.ldr = ldr; p.partial = workspace; p.xcd_split = 0; p.accumulate = 0;
-    p.nbm = (M + 255) / 256; p.nbn = (N + 255) / 256;
+    const dma_plan::Args a = {A, B, C, a_plane_stride, b_plane_stride, lda, ldb, ldc, tn, M, N, K, bias, act, dref_h, ldr, dact, accumulate};
+    if (dma_plan::check_args(a, 16, false) != CHAM_OK) return -CHAM_ERR_ARG;
+    P3Params p = p3_params(a, workspace);
     hipStream_t st = (hipStream_t)stream;
     if (!tn) {
-        if ((K & 15) || accumulate) return -CHAM_ERR_ARG;
-        if ((size_t)256 * lda * 2 >= (1ull << 31) || (size_t)256 * ldb * 2 >= (1ull << 31)) return -CHAM_ERR_ARG;
-        p.kchunk = K; p.splits = 1;
         ++g_p3_launches[0];
-        if (dref_h && (bias || act != ACT_NONE || dact != ACT_LEAKY)) return -CHAM_ERR_ARG;
-        if (act != ACT_NONE && !(bias && act == ACT_TANH)) return -CHAM_ERR_ARG;
-        if (dref_h) return p3_launch<false, 3>(p, st);
-        if (bias) {
-            if (act == ACT_TANH) return p3_launch<false, 2>(p, st);
-            if (act == ACT_NONE) return p3_launch<false, 5>(p, st);
-            return -CHAM_ERR_ARG;
+        switch (dma_plan::nt_epilogue(bias != nullptr, act, dref_h != nullptr, dact, true)) {
+            case 0: return p3_launch<false, 0>(p, st);
+            case 2: return p3_launch<false, 2>(p, st);
+            case 3: return p3_launch<false, 3>(p, st);
+            case 5: return p3_launch<false, 5>(p, st);
+            default: return -CHAM_ERR_ARG;
         }
-        if (act != ACT_NONE) return -CHAM_ERR_ARG;
-        return p3_launch<false, 0>(p, st);
     }
-    if ((M & 255) || (N & 255) || bias || act != ACT_NONE || dref_h) return -CHAM_ERR_ARG;
-    if ((size_t)16 * lda * 2 >= (1ull << 31) || (size_t)16 * ldb * 2 >= (1ull << 31)) return -CHAM_ERR_ARG;
-    const long tiles = (long)p.nbm * p.nbn;
-    int splits = 1;
-    if (splits_hint != 1 && workspace) {
-        long want = splits_hint > 1 ? splits_hint : (tiles >= 192 ? 1 : (256 + tiles - 1) / tiles);      // one workgroup per CU
-        const long maxk = (K + 511) / 512;
-        if (want > maxk) want = maxk;
-        const long maxw = (long)(workspace_bytes / ((size_t)M * N * sizeof(float)));
-        if (want > maxw) want = maxw;
-        if (splits_hint <= 0 && want >= 8) want = want / 8 * 8;      // an explicit count is taken as given (e.g. 14 x 16 tiles = 224 workgroups: one round that leaves 32 CUs to the kernels of the other lane)
-        if (want > 1) splits = (int)want;
-    }
-    int kchunk = (K + splits - 1) / splits;
-    kchunk = ((kchunk + 15) / 16) * 16;
-    p.kchunk = kchunk;
-    p.splits = (K + kchunk - 1) / kchunk;
-    if ((size_t)kchunk * (lda > ldb ? lda : ldb) * 2 >= 0xFFFFFFF0ull) return -CHAM_ERR_ARG;
+    dma_plan::SplitPlan plan;
+    if (dma_plan::plan_tn_splits(M, N, K, lda, ldb, workspace != nullptr, workspace_bytes, splits_hint, 16, 512, plan) != CHAM_OK) return -CHAM_ERR_ARG;
     ++g_p3_launches[1];
-    if (p.splits > 1) {
-        p.xcd_split = (p.splits % 8 == 0) ? 1 : 0;
-        const int rc = p3_launch<true, 6>(p, st);
-        if (rc != CHAM_OK) return rc;
-        GemmParams g;
-        g.A = nullptr; g.B = nullptr; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = 0; g.ldb = 0; g.ldc = ldc; g.bias = nullptr; g.act = ACT_NONE;
-        g.dref = nullptr; g.ldr = 0; g.dact = ACT_NONE; g.rs = nullptr; g.ldrs = 0; g.rs_div = 1; g.accumulate = accumulate;
-        g.kchunk = kchunk; g.splits = p.splits; g.partial = workspace; g.nbm = p.nbm; g.nbn = p.nbn; g.xcd_split = p.xcd_split;
-        launch_splitk_reduce(g, st);
-        CHAM_CHECK_LAUNCH();
-        return CHAM_OK;
-    }
-    p.accumulate = accumulate;
-    return p3_launch<true, 0>(p, st);
+    return dma_launch_tn<gemm_p3_kernel<true, 6>, gemm_p3_kernel<true, 0>, P3_SMEM>(p, plan, accumulate, g_p3_launches, st);
 }
 
 // ---- bf16 configuration: one bf16 plane per operand on the LDS-DMA core (gemm_b1_kernel above)
@@ -914,93 +804,29 @@ extern "C" int cham_gemm_p3(const void* A, long long a_plane_stride, int lda, co
 //   tn = 1 (TN): A stored [K, lda >= M], B stored [K, ldb >= N] bf16; M % 256 == 0, N % 256 == 0; C fp32 [M, ldc] (+= with accumulate),
 //     split-K through `workspace` (splits_hint as cham_gemm_p3; fixed-order reduction).
 // Returns -CHAM_ERR_ARG for shapes it does not take (the caller keeps cham_gemm_b16 for those).  Launch counters: [2] NT, [3] TN.
-template <bool TN, int EPI>
-static int b1_launch(P3Params& p, hipStream_t st) {
-    g_p3_launches[6] = EPI; g_p3_launches[7] = p.splits;
-    constexpr int smem = P3_RING * P3_STAGE;
-    auto k = gemm_b1_kernel<TN, EPI>;
-    CHAM_SET_DYNAMIC_LDS(k, smem);
-    hipLaunchKernelGGL(k, dim3(p.nbm * p.nbn, p.splits, 1), dim3(512), smem, st, p);
-    CHAM_CHECK_LAUNCH();
-    return CHAM_OK;
-}
-
 // NT launches take the 64-byte-piece kernel (gemm_b1w_kernel) when K % 64 == 0, unless switched off (A/B arm, tests): launch counter [4]
 static int g_b1_nt_wide = 1;
 extern "C" int cham_gemm_b16_dma_set_nt_wide(int on) { const int was = g_b1_nt_wide; g_b1_nt_wide = on ? 1 : 0; return was; }
-template <int EPI>
-static int b1w_launch(P3Params& p, hipStream_t st) {
-    g_p3_launches[6] = EPI; g_p3_launches[7] = 1; ++g_p3_launches[4];
-    constexpr int smem = 2 * B1W_BUF;
-    auto k = gemm_b1w_kernel<EPI>;
-    CHAM_SET_DYNAMIC_LDS(k, smem);
-    hipLaunchKernelGGL(k, dim3(p.nbm * p.nbn, 1, 1), dim3(512), smem, st, p);
-    CHAM_CHECK_LAUNCH();
-    return CHAM_OK;
-}
 
 extern "C" int cham_gemm_b16_dma(const void* A, int lda, const void* B, int ldb, int tn, void* C, int ldc, int M, int N, int K,
                                  const float* bias, int act, const void* dref, int ldr, int dact, int accumulate, float* workspace,
                                  size_t workspace_bytes, int splits_hint, void* stream) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return -CHAM_ERR_ARG;
-    if ((lda & 7) || (ldb & 7) || (N & 3) || (ldc & 3) || (dref && (ldr & 3))) return -CHAM_ERR_ARG;
-    if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)dref | (uintptr_t)bias) & 15) return -CHAM_ERR_ARG;
-    if ((size_t)ldc * 4 * 256 >= WINDOW_BYTES || (size_t)ldr * 2 * 256 >= WINDOW_BYTES) return -CHAM_ERR_ARG;
-    if (lda < (tn ? M : K) || ldb < (tn ? N : K) || ldc < N || (dref && ldr < N)) return -CHAM_ERR_ARG;      // leading dimension < the extent it strides over
-    P3Params p;
-    p.A = reinterpret_cast<const __bf16*>(A); p.B = reinterpret_cast<const __bf16*>(B); p.a_ps = 0; p.b_ps = 0;
-    p.lda = lda; p.ldb = ldb; p.C = reinterpret_cast<float*>(C); p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.bias = bias;
-    p.dref = reinterpret_cast<const __bf16*>(dref); p.ldr = ldr; p.partial = workspace; p.xcd_split = 0; p.accumulate = 0;
-    p.nbm = (M + 255) / 256; p.nbn = (N + 255) / 256;
+    const dma_plan::Args a = {A, B, C, 0, 0, lda, ldb, ldc, tn, M, N, K, bias, act, dref, ldr, dact, accumulate};
+    if (dma_plan::check_args(a, 48, true) != CHAM_OK) return -CHAM_ERR_ARG;
+    P3Params p = p3_params(a, workspace);
     hipStream_t st = (hipStream_t)stream;
     if (!tn) {
-        if ((K & 15) || accumulate) return -CHAM_ERR_ARG;
-        if ((size_t)256 * lda * 2 >= (1ull << 31) || (size_t)256 * ldb * 2 >= (1ull << 31)) return -CHAM_ERR_ARG;
-        p.kchunk = K; p.splits = 1;
         ++g_p3_launches[2];
-        const bool wide = g_b1_nt_wide && (K & 63) == 0;
-        if (dref) {
-            if (bias || act != ACT_NONE || dact != ACT_LEAKY) return -CHAM_ERR_ARG;
-            return wide ? b1w_launch<13>(p, st) : b1_launch<false, 13>(p, st);
+        const int epi = dma_plan::nt_epilogue(bias != nullptr, act, dref != nullptr, dact, false);
+        if (epi < 0) return -CHAM_ERR_ARG;
+        if (g_b1_nt_wide && (K & 63) == 0) {
+            ++g_p3_launches[4];
+            return epi == 3 ? b1w_launch<13>(p, st) : (epi == 2 ? b1w_launch<12>(p, st) : b1w_launch<10>(p, st));
         }
-        if (bias) {
-            if (act != ACT_TANH) return -CHAM_ERR_ARG;
-            return wide ? b1w_launch<12>(p, st) : b1_launch<false, 12>(p, st);
-        }
-        if (act != ACT_NONE) return -CHAM_ERR_ARG;
-        return wide ? b1w_launch<10>(p, st) : b1_launch<false, 10>(p, st);
+        return epi == 3 ? b1_launch<false, 13>(p, st) : (epi == 2 ? b1_launch<false, 12>(p, st) : b1_launch<false, 10>(p, st));
     }
-    if ((M & 255) || (N & 255) || bias || act != ACT_NONE || dref) return -CHAM_ERR_ARG;
-    if ((size_t)48 * lda * 2 >= (1ull << 31) || (size_t)48 * ldb * 2 >= (1ull << 31)) return -CHAM_ERR_ARG;
-    const long tiles = (long)p.nbm * p.nbn;
-    int splits = 1;
-    if (splits_hint != 1 && workspace) {
-        long want = splits_hint > 1 ? splits_hint : (tiles >= 192 ? 1 : (256 + tiles - 1) / tiles);
-        const long maxk = (K + 1535) / 1536;
-        if (want > maxk) want = maxk;
-        const long maxw = (long)(workspace_bytes / ((size_t)M * N * sizeof(float)));
-        if (want > maxw) want = maxw;
-        if (splits_hint <= 0 && want >= 8) want = want / 8 * 8;
-        if (want > 1) splits = (int)want;
-    }
-    int kchunk = (K + splits - 1) / splits;
-    kchunk = ((kchunk + 47) / 48) * 48;
-    p.kchunk = kchunk;
-    p.splits = (K + kchunk - 1) / kchunk;
-    if ((size_t)kchunk * (lda > ldb ? lda : ldb) * 2 >= 0xFFFFFFF0ull) return -CHAM_ERR_ARG;
+    dma_plan::SplitPlan plan;
+    if (dma_plan::plan_tn_splits(M, N, K, lda, ldb, workspace != nullptr, workspace_bytes, splits_hint, 48, 1536, plan) != CHAM_OK) return -CHAM_ERR_ARG;
     ++g_p3_launches[3];
-    if (p.splits > 1) {
-        p.xcd_split = (p.splits % 8 == 0) ? 1 : 0;
-        const int rc = b1_launch<true, 6>(p, st);
-        if (rc != CHAM_OK) return rc;
-        GemmParams g;
-        g.A = nullptr; g.B = nullptr; g.C = reinterpret_cast<float*>(C); g.M = M; g.N = N; g.K = K; g.lda = 0; g.ldb = 0; g.ldc = ldc; g.bias = nullptr;
-        g.act = ACT_NONE; g.dref = nullptr; g.ldr = 0; g.dact = ACT_NONE; g.rs = nullptr; g.ldrs = 0; g.rs_div = 1; g.accumulate = accumulate;
-        g.kchunk = kchunk; g.splits = p.splits; g.partial = workspace; g.nbm = p.nbm; g.nbn = p.nbn; g.xcd_split = p.xcd_split;
-        launch_splitk_reduce(g, st);
-        CHAM_CHECK_LAUNCH();
-        return CHAM_OK;
-    }
-    p.accumulate = accumulate;
-    return b1_launch<true, 0>(p, st);
+    return dma_launch_tn<gemm_b1_kernel<true, 6>, gemm_b1_kernel<true, 0>, P3_SMEM>(p, plan, accumulate, g_p3_launches, st);
 }

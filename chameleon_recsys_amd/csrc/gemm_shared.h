@@ -1,9 +1,12 @@
 // Pieces shared by the GEMM translation units (gemm.hip: native fp32 MFMA and the on-the-fly bf16 variant; gemm_x3.hip: fp32 through
-// three bf16 planes): the parameter block, tile windows, the common epilogue, the bf16 staging loader and the split-K reduction.
+// three bf16 planes; gemm_b16.hip: bf16-resident operands; gemm_dma.h: the LDS-DMA core of gemm_p3.hip and gemm_h2.hip): the parameter
+// block, tile windows, the workgroup -> tile map, the common epilogue, the bf16 staging loader and the split-K reduction.
 #pragma once
 #include "common.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
 #define OOB_OFF 0x80000000u          // > every window size below: loads return 0, stores are dropped
 #define WINDOW_BYTES 0x7FFFF000
 
@@ -12,6 +15,42 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_window(const void* base) 
 }
 __device__ __forceinline__ float4 as_f4(u32x4 v) {
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+}
+// the two bf16 of a 32-bit word as fp32 (exact), and back (v_cvt_pk_bf16_f32: round to nearest even)
+__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
+__device__ __forceinline__ unsigned pack_bf2(float a, float b) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    bf16x2 v; v[0] = (__bf16)a; v[1] = (__bf16)b;
+    return __builtin_bit_cast(unsigned, v);
+}
+
+// ---- XCD-aware, bijective workgroup -> (tile, K-split) map (all scalar) for a grid of (nbm * nbn, K-splits) workgroups.  Workgroups are
+// dealt to the 8 XCDs round-robin in dispatch order.
+//   xcd_split: split-K with a small output (wgrad): ALL tiles of one K-split on the same XCD, so that each K-panel of A and B is fetched
+//     from HBM once and shared through that XCD's L2 (tile-major placement re-read every panel on ~3 XCDs: the W2 wgrad fetched 6.3 GB for
+//     2.07 GB of operands).  The host sets it for whole groups of 8 splits only.
+//   otherwise: consecutive tile ids - the column tiles of one A panel - share an XCD's L2; blockIdx.y is the K-split.
+// P: a parameter block with nbm, nbn, xcd_split.  SPLITK = false: the kernels without K-splits (grid = nbm * nbn workgroups).
+// (The results leave through locals assigned once at the end: with the references written in the branches some kernels came out with
+// another register allocation than the block had inline - scripts/kernel_isa_diff.py.)
+template <bool SPLITK = true, class P>
+__device__ __forceinline__ void gemm_tile_map(const P& p, int& tile_m, int& tile_n, int& split) {
+    const int nwg = p.nbm * p.nbn;
+    int tm, tn, sp;
+    if (SPLITK && p.xcd_split) {
+        const int lin = blockIdx.x + gridDim.x * blockIdx.y, slot = lin >> 3;
+        sp = (lin & 7) + 8 * (slot / nwg);
+        const int t = slot % nwg;
+        tm = t / p.nbn; tn = t % p.nbn;
+    } else {
+        const int id = blockIdx.x;
+        const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
+        const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
+        tm = swz / p.nbn; tn = swz % p.nbn;
+        sp = SPLITK ? blockIdx.y : 0;
+    }
+    tile_m = tm; tile_n = tn; split = sp;
 }
 
 struct GemmParams {
@@ -252,6 +291,9 @@ struct TileLoaderBF {
 };
 
 
+// (GEMM_SHARED_NO_SPLITK_REDUCE: gemm_b16.hip keeps reducers of its own - another wide / plain threshold, i.e. another summation order for
+// some shapes - and a `static __global__` kernel is emitted whether or not the file launches it)
+#ifndef GEMM_SHARED_NO_SPLITK_REDUCE
 // fixed-order reduction of split-K partials (+ the generic epilogue).  Four consecutive columns per thread (16-byte loads of every
 // partial slab, four slabs in flight), the slabs added in ascending split order exactly as the scalar form did (bit-identical sums).
 // Round 2's one-element-per-thread form with a 64-bit divide per element cost 1.1 ms per step over its ten launches.
@@ -337,6 +379,7 @@ static inline void launch_splitk_reduce(const GemmParams& p, hipStream_t st) {
         hipLaunchKernelGGL(gemm_splitk_reduce, dim3(blocks), dim3(256), 0, st, p);
     }
 }
+#endif
 
 
 // Argument checks + the split-K plan shared by every precision (host side).

@@ -241,20 +241,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_x3_kernel(GemmParams p) {
     __bf16* As = reinterpret_cast<__bf16*>(smem);      // [2][3][plane]
     __bf16* Bs = As + 2 * ASZ;                         // [2][3][plane]
 
-    const int nwg = p.nbm * p.nbn;
     int tile_m, tile_n, split;
-    if (p.xcd_split) {                                 // one K-split per XCD (see gemm.hip)
-        const int lin = blockIdx.x + gridDim.x * blockIdx.y, slot = lin >> 3;
-        split = (lin & 7) + 8 * (slot / nwg);
-        const int t = slot % nwg;
-        tile_m = t / p.nbn; tile_n = t % p.nbn;
-    } else {
-        const int id = blockIdx.x;
-        const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-        const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-        tile_m = swz / p.nbn; tile_n = swz % p.nbn;
-        split = blockIdx.y;
-    }
+    gemm_tile_map(p, tile_m, tile_n, split);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int kbeg = split * p.kchunk;
     const int kend = min(p.K, kbeg + p.kchunk);
