@@ -667,6 +667,7 @@ class StepPlan:
         self.logits, self.probs = f32(BT, NC), f32(BT, NC)
         self.nll = f32(BT)
         self.nov_aux = f32(BT, 3)
+        self.div_sp = self.div_e = None       # --diversity_reg_factor > 0: S p [BT, NC] and p^T S p [BT] of the step (ensure_diversity)
         self.mask = torch.zeros(BT, dtype=torch.uint8, device=dev)
         self.loss = torch.zeros(3, dtype=torch.float32, device=dev)
         # valid-position compaction (see NARModuleModel.upload_batch): compact copies of the sampler output, and the
@@ -699,6 +700,15 @@ class StepPlan:
             setattr(self, name, t)
             self.nbytes = self.allocated_bytes()         # what the plan cache's byte budget counts (NARRuntime.plan)
         return t
+
+    def ensure_diversity(self):
+        """The two buffers of the content-diversity term (csrc/diversity.hip), allocated on the first step of a model that has it."""
+        if self.div_sp is None:
+            dev = self.probs.device
+            self.div_sp = torch.empty(self.BT, self.NC, dtype=torch.float32, device=dev)
+            self.div_e = torch.empty(self.BT, dtype=torch.float32, device=dev)
+            self.nbytes = self.allocated_bytes()
+        return self.div_sp, self.div_e
 
     def cand_Z1(self, P=None):
         """Candidate rows of the PreCAR output of the last step as fp32 [P * NC, C] (tests): the fp32 matrix, or the sum of its planes."""
@@ -743,6 +753,10 @@ class NARModuleModel:
         self.elapsed_days_smooth_log_base = float(elapsed_days_smooth_log_base)
         self.popularity_smooth_log_base = float(popularity_smooth_log_base)
         self.novelty_reg_factor = float(novelty_reg_factor)
+        # content-diversity regulariser (the reference's commented-out loss, nar_model.py:551-636, 685-702)
+        self.diversity_reg_factor = float(diversity_reg_factor)
+        if not (self.diversity_reg_factor >= 0.0):
+            raise ValueError("diversity_reg_factor must be >= 0")
         self.is_training = (mode == ModeKeys.TRAIN)
         if self.is_training and not (0.0 < keep_prob <= 1.0):
             raise ValueError("dropout_keep_prob must be in (0, 1]")
@@ -1114,6 +1128,11 @@ class NARModuleModel:
         check(getattr(lib, arm.softmax_fwd)(ptr(pl.S3), 32, ptr(p('Ws4')), ptr(p('bs4')), BT, N, float(self.softmax_temperature),
                                             ptr(pl.mask), ptr(pl.logits), ptr(pl.probs), ptr(pl.nll), self.novelty_reg_factor,
                                             ptr(neg_ids), ptr(st['pop_norm']), ptr(pl.nov_aux), s), "cham_score_softmax_fwd")
+        if self.diversity_reg_factor > 0.0:      # + factor * p^T S p into nll, ahead of the loss record below (TRAIN and EVAL)
+            sp, e = pl.ensure_diversity()
+            check(lib.cham_diversity_fwd(ptr(pl.probs), ptr(d['ln_rows']), ptr(neg_ids), ptr(pl.mask), BT, N, ptr(rt.ace), rt.ace.stride(0),
+                                         rt.ace.shape[1], rt.ace.shape[0], self.diversity_reg_factor, ptr(sp), ptr(e), ptr(pl.nll), s),
+                  "cham_diversity_fwd")
         def loss_kernels(s):
             check(lib.cham_sumsq_partial(ptr(rt.flat), L.n_reg, ptr(rt.sumsq), s), "cham_sumsq_partial")
             fn, sum_mask = step_scalar(rt, 'cham_loss_finalize', d['sum_mask'])      # (from the step-scalar record, or by value)
@@ -1200,6 +1219,11 @@ class NARModuleModel:
             ptr(pl.S3), 32, ptr(p('Ws4')), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
             ptr(rt.scalars) if rt.dev_scalars else d['sum_mask'], ptr(pl.ds), ptr(pl.dS3), self.novelty_reg_factor, ptr(neg_ids),
             ptr(self._dev_state['pop_norm']), ptr(pl.logits), ptr(pl.nov_aux), s), "cham_score_softmax_bwd")
+        if self.diversity_reg_factor > 0.0:      # ds += the diversity term's logit gradient, dS3 again from it
+            check(getattr(lib, arm.diversity_bwd)(
+                ptr(pl.S3), 32, ptr(p('Ws4')), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
+                ptr(rt.scalars) if rt.dev_scalars else None, 0.0 if rt.dev_scalars else d['sum_mask'], ptr(pl.div_sp), ptr(pl.div_e),
+                self.diversity_reg_factor, ptr(pl.ds), ptr(pl.dS3), s), arm.diversity_bwd)
         if self._dev_state.get('device'):
             self.articles_recent_pop_norm.note_consumed(d['aci'])      # last read of the state in a TRAIN step
         # scorer dgrad chain on this lane (three short GEMMs); the side lane takes the layer-1 weight gradient FIRST - 65 GFLOP of
@@ -1546,9 +1570,12 @@ class NARModuleModel:
     def outputs_numpy(self):
         pl = self._plan
         torch.cuda.synchronize()
-        return dict(loss=pl.loss.cpu().numpy(), logits=pl.full_rows(pl.logits).view(pl.B, pl.T, pl.NC).cpu().numpy(),
-                    probs=pl.full_rows(pl.probs).view(pl.B, pl.T, pl.NC).cpu().numpy(), neg_items=pl.neg_ids.cpu().numpy(),
-                    neg_slot=pl.neg_slot.cpu().numpy(), pool=pl.pool.cpu().numpy(), meta=pl.meta.cpu().numpy())
+        out = dict(loss=pl.loss.cpu().numpy(), logits=pl.full_rows(pl.logits).view(pl.B, pl.T, pl.NC).cpu().numpy(),
+                   probs=pl.full_rows(pl.probs).view(pl.B, pl.T, pl.NC).cpu().numpy(), neg_items=pl.neg_ids.cpu().numpy(),
+                   neg_slot=pl.neg_slot.cpu().numpy(), pool=pl.pool.cpu().numpy(), meta=pl.meta.cpu().numpy())
+        if self.diversity_reg_factor > 0.0:      # p^T S p per click (zeros at padded positions)
+            out['div_e'] = pl.full_rows(pl.div_e).view(pl.B, pl.T).cpu().numpy()
+        return out
 
 
 class GraphedTrainStep:
@@ -1594,6 +1621,8 @@ class GraphedTrainStep:
             return "data-parallel exchange inside the step"
         if m.keep_prob < 1.0 or m.eval_cold_start or not m.is_training or not rt.presample:
             return "dropout / cold-start analysis / presampling off"
+        if m.diversity_reg_factor > 0.0:
+            return "diversity regulariser (its two launches are not part of the captured step)"
         if self.key is not None and self.shape_key(d) != self.key:
             return "another batch shape than the captured one"
         if self.graph is None:      # capture needs a warm shape: buffers, workspaces, the step-scalar record and the kernels' dynamic-LDS

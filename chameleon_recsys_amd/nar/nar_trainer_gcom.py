@@ -63,7 +63,10 @@ def define_flags():
     a('--disable_eval_benchmarks', type=_bool, default=False, nargs='?', const=True, help='Disable eval benchmarks')
     a('--eval_metrics_by_session_position', type=_bool, default=False, nargs='?', const=True)
     a('--novelty_reg_factor', type=float, default=0.0)
-    a('--diversity_reg_factor', type=float, default=0.0)
+    a('--diversity_reg_factor', type=float, default=0.0,
+      help="weight (>= 0) of the content-diversity regulariser added to the loss: factor x the mean over valid clicks of p^T S p, p the softmax "
+           "over the click's candidates and S their pairwise content-embedding cosine similarity, 0 between candidates of equal id (the "
+           "reference's commented-out loss, nar_model.py:551-636, 685-702); 0 = off")
     a('--eval_negative_sample_relevance', type=float, default=0.1)
     a('--content_embedding_scale_factor', type=float, default=1.0)
     a('--enabled_clicks_input_features_groups', type=_list, default=[ALL_FEATURES])

@@ -478,6 +478,26 @@ int cham_score_softmax_fwd(const float* S3, int K3, const float* w4, const float
 int cham_score_softmax_bwd(const float* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N,
                            float tau, float sum_mask, float* ds, float* dS3, float novelty_reg_factor, const int64_t* neg_ids,
                            const float* pop_norm, const float* logits, const float* nov_aux, void* stream);
+/* diversity_reg_factor > 0 adds the content-diversity regulariser of nar_model.py:551-636, 685-702 (commented out in the reference) to
+ * the per-click loss: + factor * p^T S p, p = probs [BT,1+N] of the click, S_cc' = e^_c . e^_c' for candidates of DIFFERENT ids and 0 for
+ * equal ids (the diagonal of the unique-id similarity matrix: zero padding of short negative lists included),
+ * e^_c = ace[id_c] / sqrt(max(|ace[id_c]|^2, 1e-12)); id_0 = label_ids[bt], id_c = neg_ids[bt, c-1]; ace [n_items, D] with row stride
+ * ld_ace >= D elements (an id outside [0, n_items) counts as an all-zero row).  csrc/diversity.hip.
+ *   cham_diversity_fwd: sp [BT,1+N] = S p, e [BT] = p^T S p, nll[bt] += factor * e[bt]; a masked click gathers nothing, gets sp = 0 and
+ *     e = 0 and leaves nll[bt] alone.  Runs behind cham_score_softmax_fwd[_b16].  Fixed summation order, no atomics.
+ *   cham_diversity_bwd[_b16]: behind cham_score_softmax_bwd[_b16][_dev] of the same S3 storage:
+ *     ds[row] += factor * mask / (tau * sum_mask) * 2 p_c (sp_c - e) and dS3[row,k] = ds[row] * w4[k] * leaky'(S3[row,k]) rewritten from the
+ *     updated ds in that kernel's operation order.  sum(mask) comes from the step-scalar record `scalars` when it is not NULL, else from
+ *     `sum_mask` by value - the same fp32 expression either way.  K3 == 32. */
+int cham_diversity_fwd(const float* probs, const int64_t* label_ids, const int64_t* neg_ids, const uint8_t* mask, int BT, int N,
+                       const float* ace, int ld_ace, int D, int64_t n_items, float diversity_reg_factor, float* sp, float* e, float* nll,
+                       void* stream);
+int cham_diversity_bwd(const float* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N, float tau,
+                       const void* scalars, float sum_mask, const float* sp, const float* e, float diversity_reg_factor, float* ds,
+                       float* dS3, void* stream);
+int cham_diversity_bwd_b16(const void* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N, float tau,
+                           const void* scalars, float sum_mask, const float* sp, const float* e, float diversity_reg_factor, float* ds,
+                           void* dS3, void* stream);
 
 /* evaluation: rank_items_by_predicted_prob, nar_model.py:777-794 (tf.nn.top_k over 1+N: descending, lowest index wins
  * ties).  pred_ids/pred_probs [BT, 1+N]; label_rank[bt] = 0-based rank of the positive, -1 for padded clicks - the input of
