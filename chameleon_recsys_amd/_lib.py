@@ -115,6 +115,12 @@ _SIGNATURES = {
     "cham_diversity_fwd": (c_int, [P, P, P, P, c_int, c_int, P, c_int, c_int, c_int64, c_float, P, P, P, P]),
     "cham_diversity_bwd": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, P, c_float, P, P, c_float, P, P, P]),
     "cham_diversity_bwd_b16": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, P, c_float, P, P, c_float, P, P, P]),
+    "cham_cosine_fwd": (c_int, [P, c_int64, P, c_int, c_int, c_int, P, P, P, P]),
+    "cham_cosine_fwd_b16": (c_int, [P, c_int64, P, c_int, c_int, c_int, P, P, P, P]),
+    "cham_cosine_bound": (c_int, [P, P, c_size_t, P, P]),
+    "cham_cosine_bwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
+    "cham_cosine_bwd_h2": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, c_int64, P, P, P, P]),
+    "cham_cosine_bwd_b16": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
     "cham_rank_items": (c_int, [P, P, P, P, c_int, c_int, P, P, P, P]),
     "cham_state_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cham_state_update": (c_int, [P, P, c_int, c_int, c_double, P, P, c_int, P, P, P, c_int, c_int, P, P, c_size_t, P]),

@@ -167,12 +167,17 @@ static int diversity_bwd_impl(const T* S3, int K3, const float* w4, const float*
                               const void* scalars, float sum_mask, const float* sp, const float* e, float factor, float* ds, T* dS3,
                               void* stream) {
     if (!S3 || !w4 || !probs || !mask || !sp || !e || !ds || !dS3) return -CHAM_ERR_ARG;
-    if (K3 != 32 || BT < 0 || N < 1 || !(factor >= 0.f) || (!scalars && !(sum_mask > 0.f))) return -CHAM_ERR_ARG;
+    if ((K3 != 32 && K3 != 4) || BT < 0 || N < 1 || !(factor >= 0.f) || (!scalars && !(sum_mask > 0.f))) return -CHAM_ERR_ARG;
     const size_t rows = (size_t)BT * ((size_t)N + 1);
     if (rows == 0) return CHAM_OK;
-    hipLaunchKernelGGL((k_diversity_bwd<32, T>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S3, w4, probs, mask,
-                       BT, N, scalars ? 0.f : 1.0f / (tau * sum_mask), reinterpret_cast<const ChamStepScalars*>(scalars), tau, sp, e, factor,
-                       ds, dS3);
+    if (K3 == 4)      // the cosine head (csrc/cosine.hip): ds is what its backward reads, dS3 [rows, 4] is scratch
+        hipLaunchKernelGGL((k_diversity_bwd<4, T>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S3, w4, probs, mask,
+                           BT, N, scalars ? 0.f : 1.0f / (tau * sum_mask), reinterpret_cast<const ChamStepScalars*>(scalars), tau, sp, e, factor,
+                           ds, dS3);
+    else
+        hipLaunchKernelGGL((k_diversity_bwd<32, T>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S3, w4, probs, mask,
+                           BT, N, scalars ? 0.f : 1.0f / (tau * sum_mask), reinterpret_cast<const ChamStepScalars*>(scalars), tau, sp, e, factor,
+                           ds, dS3);
     CHAM_CHECK_LAUNCH();
     return CHAM_OK;
 }

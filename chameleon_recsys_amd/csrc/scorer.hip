@@ -797,10 +797,15 @@ template <typename T>
 static int score_softmax_fwd_impl(const T* S3, int K3, const float* w4, const float* b4, int BT, int N, float tau,
                                   const uint8_t* mask, float* logits, float* probs, float* nll, float novelty_reg_factor,
                                   const int64_t* neg_ids, const float* pop_norm, float* nov_aux, void* stream) {
-    if (!S3 || !w4 || !b4 || !mask || !logits || !probs || !nll || K3 != 32 || BT <= 0 || N <= 0) return -CHAM_ERR_ARG;
+    if (!S3 || !w4 || !b4 || !mask || !logits || !probs || !nll || (K3 != 32 && K3 != 4) || BT <= 0 || N <= 0) return -CHAM_ERR_ARG;
     if (novelty_reg_factor > 0.f && (!neg_ids || !pop_norm || !nov_aux)) return -CHAM_ERR_ARG;
-    hipLaunchKernelGGL((k_score_softmax_fwd<32, T>), dim3((BT + 3) / 4), dim3(256), 0, (hipStream_t)stream, S3, w4, b4, BT, N,
-                       1.0f / tau, mask, logits, probs, nll, novelty_reg_factor, neg_ids, pop_norm, nov_aux, g_cham_inv_log2_pop_base);
+    // K3 == 4: the cosine head (csrc/cosine.hip) - S3 = (cos, 0, 0, 0) per row, w4 = (1, 0, 0, 0), b4 = 0: the dot below returns cos unchanged
+    if (K3 == 4)
+        hipLaunchKernelGGL((k_score_softmax_fwd<4, T>), dim3((BT + 3) / 4), dim3(256), 0, (hipStream_t)stream, S3, w4, b4, BT, N,
+                           1.0f / tau, mask, logits, probs, nll, novelty_reg_factor, neg_ids, pop_norm, nov_aux, g_cham_inv_log2_pop_base);
+    else
+        hipLaunchKernelGGL((k_score_softmax_fwd<32, T>), dim3((BT + 3) / 4), dim3(256), 0, (hipStream_t)stream, S3, w4, b4, BT, N,
+                           1.0f / tau, mask, logits, probs, nll, novelty_reg_factor, neg_ids, pop_norm, nov_aux, g_cham_inv_log2_pop_base);
     CHAM_CHECK_LAUNCH();
     return CHAM_OK;
 }
@@ -822,12 +827,17 @@ static int score_softmax_bwd_impl(const T* S3, int K3, const float* w4, const fl
                                   int BT, int N, float tau, float sum_mask, float* ds, T* dS3, float novelty_reg_factor,
                                   const int64_t* neg_ids, const float* pop_norm, const float* logits, const float* nov_aux,
                                   void* stream, const void* scalars = nullptr) {
-    if (!S3 || !w4 || !probs || !mask || !ds || !dS3 || K3 != 32 || BT <= 0 || (!scalars && sum_mask <= 0.f)) return -CHAM_ERR_ARG;
+    if (!S3 || !w4 || !probs || !mask || !ds || !dS3 || (K3 != 32 && K3 != 4) || BT <= 0 || (!scalars && sum_mask <= 0.f)) return -CHAM_ERR_ARG;
     if (novelty_reg_factor > 0.f && (!neg_ids || !pop_norm || !logits || !nov_aux)) return -CHAM_ERR_ARG;
     const size_t rows = (size_t)BT * (N + 1);
-    hipLaunchKernelGGL((k_score_softmax_bwd<32, T>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S3, w4,
-                       probs, mask, BT, N, scalars ? 0.f : 1.0f / (tau * sum_mask), ds, dS3, novelty_reg_factor, neg_ids, pop_norm, logits,
-                       1.0f / tau, nov_aux, g_cham_inv_log2_pop_base, reinterpret_cast<const ChamStepScalars*>(scalars), tau);
+    if (K3 == 4)      // the cosine head: ds is what its backward reads, dS3 [rows, 4] is scratch
+        hipLaunchKernelGGL((k_score_softmax_bwd<4, T>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S3, w4,
+                           probs, mask, BT, N, scalars ? 0.f : 1.0f / (tau * sum_mask), ds, dS3, novelty_reg_factor, neg_ids, pop_norm, logits,
+                           1.0f / tau, nov_aux, g_cham_inv_log2_pop_base, reinterpret_cast<const ChamStepScalars*>(scalars), tau);
+    else
+        hipLaunchKernelGGL((k_score_softmax_bwd<32, T>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S3, w4,
+                           probs, mask, BT, N, scalars ? 0.f : 1.0f / (tau * sum_mask), ds, dS3, novelty_reg_factor, neg_ids, pop_norm, logits,
+                           1.0f / tau, nov_aux, g_cham_inv_log2_pop_base, reinterpret_cast<const ChamStepScalars*>(scalars), tau);
     CHAM_CHECK_LAUNCH();
     return CHAM_OK;
 }

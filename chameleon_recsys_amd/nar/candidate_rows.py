@@ -143,6 +143,17 @@ class F32Rows:
     def dense_dZ1(self, pl, st):      # dZ1 of all CAR rows as one fp32 matrix (dense PreCAR backward of the dropout path)
         return pl.dZ1
 
+    # ---- the cosine head (--recommendations_ranking cosine; csrc/cosine.hip) over this arm's storage
+    def cosine_fwd(self, pl, s):      # cos(pred, candidate row) -> pl.cosq [R, 4] = (cos, 0, 0, 0), the inverse norms pl.rz [R] / pl.rp [P]
+        P, C = pl.P, pl.C
+        check(self.rt.lib.cham_cosine_fwd(ptr(pl.Z2[P:P + pl.PC]), C, ptr(pl.pred), C, P, pl.N, ptr(pl.cosq), ptr(pl.rz), ptr(pl.rp), s), "cham_cosine_fwd")
+
+    def cosine_bwd(self, pl, s):      # ds -> the gradient at the CAR tanh + dpred: what scorer_dgrad + s1_dgrad + s1_wgrad + small_wgrads + dz2 are to the MLP head
+        P, R = pl.P, pl.PC
+        pl.ensure_rows('dZ2')
+        check(self.rt.lib.cham_cosine_bwd(ptr(pl.Z2[P:P + R]), ptr(pl.pred), ptr(pl.ds), ptr(pl.rz), ptr(pl.rp), ptr(pl.cosq), ptr(pl.mask), pl.C, P, pl.N,
+                                          ptr(pl.dZ2[P:P + R]), ptr(pl.dpred), None, s), "cham_cosine_bwd")
+
     def combine_bwd(self, pl, ws, st):      # dZ1 -> dU (per click) and dV (per item row) by the deterministic slot scatter
         check(self.rt.lib.cham_combine_bwd(ptr(pl.dZ1), pl.C, pl.P, pl.N, pl.pmax, ptr(pl.cur_neg_slot), ptr(pl.dU), ptr(pl.dV), ptr(ws), ws.numel() * 4, st),
               "cham_combine_bwd")
@@ -175,7 +186,8 @@ class P3Rows(F32Rows):
         # The candidate rows of Z1 exist as planes only, and with the fused scorer dgrad those of dZ2 too: the fp32 matrices keep the
         # clicked-input rows (ensure_rows() grows them on the paths that do need all rows - dropout, NC outside the fused kernel's range)
         C, BT, Rall = pl.C, pl.BT, pl.Rall
-        pl.Z1, pl.Z2, pl.dZ2, pl.dZ1 = f32(BT, C), f32(Rall, C), f32(BT if self.fused_dz2(pl) else Rall, C), f32(Rall, C)
+        # (the cosine head's backward writes the planes directly, like the fused dgrad)
+        pl.Z1, pl.Z2, pl.dZ2, pl.dZ1 = f32(BT, C), f32(Rall, C), f32(BT if (self.fused_dz2(pl) or self.rt.cosine) else Rall, C), f32(Rall, C)
         pl.z1_tiles = pl.dz2_tiles = 0
         self.alloc_planes(pl)
         pl.p3_ps = pl.Rc * C                              # plane stride of a row-major operand ...
@@ -246,6 +258,8 @@ class H2Rows(P3Rows):
     def refresh_shadows(self, s):
         rt, C = self.rt, self.rt.layout.C
         check(rt.lib.cham_split2h(ptr(rt.p('W2')), C, C, C, ptr(rt.w2p), C * C, C, ptr(rt.w2tp), C * C, C, ptr(rt.sc_w2), 1, s), "cham_split2h")
+        if rt.cosine:      # no Ws1
+            return
         k1 = rt.layout.entries['Ws1'].shape[1]
         check(rt.lib.cham_h2_scale_rownorm(ptr(rt.p('Ws1')), C, k1, k1, None, ptr(rt.sc_ws1n), s), "cham_h2_scale_rownorm")
         if rt.dm_fused:
@@ -310,6 +324,15 @@ class H2Rows(P3Rows):
                 check(lib.cham_dm_mulpred_h2(ptr(pl.dS1), 128, 128, ptr(rt.ws1p), C * 128, ptr(Z2c), ptr(pl.pred), C, P, pl.N, ptr(pl.dZ2p), pl.dz2_ps,
                                              ptr(pl.sc_dz2), ptr(pl.dpred), ptr(pl.b2part), s), "cham_dm_mulpred_h2")
 
+    def cosine_bwd(self, pl, s):
+        # ... as two fp16 planes + this click's share of the b2 gradient; the scale record from max_r |ds_r| rz_r, which bounds every element
+        # (csrc/cosine.hip k_cosine_bound: |p^_k - cos z^_k| <= 1)
+        lib, P, R = self.rt.lib, pl.P, pl.PC
+        check(lib.cham_cosine_bound(ptr(pl.ds), ptr(pl.rz), R, ptr(pl.cos_t), s), "cham_cosine_bound")
+        check(lib.cham_h2_scale_absmax(ptr(pl.cos_t), (R + 3) & ~3, None, 0, ptr(pl.sc_dz2), s), "cham_h2_scale_absmax")
+        check(lib.cham_cosine_bwd_h2(ptr(pl.Z2[P:P + R]), ptr(pl.pred), ptr(pl.ds), ptr(pl.rz), ptr(pl.rp), ptr(pl.cosq), ptr(pl.mask), pl.C, P, pl.N,
+                                     ptr(pl.dZ2p), pl.dz2_ps, ptr(pl.sc_dz2), ptr(pl.dpred), ptr(pl.b2part), s), "cham_cosine_bwd_h2")
+
     def car_dgrad(self, pl):
         rt, C = self.rt, pl.C
         rt.gemm_h2(pl.dZ2p, pl.dz2_ps, C, pl.sc_dz2, rt.w2p, C * C, C, rt.sc_w2, 0, pl.dZ1[pl.P:], C, pl.PC, C, C, dref_h=pl.Z1p, ldr=C, dact=ACT_LEAKY,
@@ -340,6 +363,8 @@ class Bf16Rows(F32Rows):
         self.rt = rt
         if rt.layout.C % 128:
             raise ValueError("gemm_dtype='bf16' needs CAR_embedding_size % 128 == 0")
+        if rt.cosine:      # no scorer weights
+            self.SHADOWED = ('W2',)
         for name in self.SHADOWED:
             r, c = rt.layout.entries[name].shape
             rt.shadow[name] = torch.zeros(r, c, dtype=torch.bfloat16, device=rt.device)
@@ -353,7 +378,9 @@ class Bf16Rows(F32Rows):
 
     def alloc(self, pl, f32):
         pl.Z1, pl.Z2, pl.dZ2, pl.dZ1 = (f32(pl.BT, pl.C) for _ in range(4))
-        pl.Z1c, pl.Z2c, pl.dZ2c, pl.dZ1c, pl.Mc = (torch.empty(pl.Rc, pl.C, dtype=torch.bfloat16, device=self.rt.device) for _ in range(5))
+        pl.Z1c, pl.Z2c, pl.dZ2c, pl.dZ1c = (torch.empty(pl.Rc, pl.C, dtype=torch.bfloat16, device=self.rt.device) for _ in range(4))
+        if not self.rt.cosine:      # cand (.) pred, the operand of the MLP head's first layer
+            pl.Mc = torch.empty(pl.Rc, pl.C, dtype=torch.bfloat16, device=self.rt.device)
         pl.b2part = f32(pl.BT, pl.C)
 
     def cand_Z1(self, pl, P, n):
@@ -402,6 +429,14 @@ class Bf16Rows(F32Rows):
             check(rt.lib.cham_dm_mulpred_b16(ptr(pl.dS1), 128, 128, ptr(rt.shadow['Ws1']), ptr(Z2c), ptr(pl.pred), C, P, pl.N, ptr(dZ2c), ptr(pl.dpred),
                                              ptr(pl.b2part), s), "cham_dm_mulpred_b16")
 
+    def cosine_fwd(self, pl, s):      # (the cosine itself is fp32: it is never rounded to bf16)
+        C = pl.C
+        check(self.rt.lib.cham_cosine_fwd_b16(ptr(pl.Z2c), C, ptr(pl.pred), C, pl.P, pl.N, ptr(pl.cosq), ptr(pl.rz), ptr(pl.rp), s), "cham_cosine_fwd_b16")
+
+    def cosine_bwd(self, pl, s):
+        check(self.rt.lib.cham_cosine_bwd_b16(ptr(pl.Z2c), ptr(pl.pred), ptr(pl.ds), ptr(pl.rz), ptr(pl.rp), ptr(pl.cosq), ptr(pl.mask), pl.C, pl.P, pl.N,
+                                              ptr(pl.dZ2c), ptr(pl.dpred), ptr(pl.b2part), s), "cham_cosine_bwd_b16")
+
     def car_dgrad(self, pl):
         rt, C = self.rt, pl.C
         rt.gemm_b16(pl.dZ2c[:pl.PC], C, 0, rt.shadow['W2'], C, 1, pl.dZ1c, C, 0, pl.PC, C, C, dref=pl.Z1c, ldr=C, dact=ACT_LEAKY, dma=rt.b16_dma)
@@ -413,7 +448,7 @@ class Bf16Rows(F32Rows):
 
     def b2_grad(self, pl):
         rt, C = self.rt, pl.C
-        if self.fused_dz2(pl):      # the per-position sums of the stored gradient rows, written by the fused kernel
+        if self.fused_dz2(pl) or rt.cosine:      # the per-position sums of the stored gradient rows, written by the fused kernel / the cosine backward
             rt.colsum(pl.b2part, C, pl.P, C, rt.g('b2'))
         else:
             rt.colsum(pl.dZ2c[:pl.PC], C, pl.PC, C, rt.g('b2'), b16=True)

@@ -48,7 +48,13 @@ class Entry:
 class ParamLayout:
     def __init__(self, session_features_config, articles_features_config, n_items, ace_dim, CAR_embedding_size,
                  rnn_units, rnn_num_layers=1, rnn_cell='ugrnn', internal_features_config=None,
-                 max_cardinality_for_ohe=10):
+                 max_cardinality_for_ohe=10, recommendations_ranking='mlp'):
+        # 'mlp': the reference's running head, cand (.) pred -> 128 -> 64 -> 32 -> 1 (nar_model.py:444-517); 'cosine': the weight-free cosine
+        # head its comments at :435-437 describe (csrc/cosine.hip) - no Ws* / bs* entries, no match* variables
+        if recommendations_ranking not in ('mlp', 'cosine'):
+            raise ValueError("recommendations_ranking=%r: 'mlp' (the reference's running head, nar_model.py:444-517) or 'cosine' (:435-437)"
+                             % (recommendations_ranking,))
+        self.ranking = recommendations_ranking
         ifc = dict(DEFAULT_INTERNAL_FEATURES)
         if internal_features_config:
             ifc.update(internal_features_config)
@@ -145,9 +151,11 @@ class ParamLayout:
         ents += [Entry('gamma_ctx', (Fc,), True, 'gamma'), Entry('beta_ctx', (Fc,), True, 'zeros'),
                  Entry('gamma_item', (Fi,), True, 'gamma'), Entry('beta_item', (Fi,), True, 'zeros'),
                  Entry('W1c', (Fc, C), True, 'pad'), Entry('W1i', (Fi, C), True, 'pad'),
-                 Entry('W2', (C, C), True, 'pad'), Entry('Wf1', (Hp, 512), True, 'pad'), Entry('Wf2', (512, C), True, 'pad'),
-                 Entry('Ws1', (C, 128), True, 'pad'), Entry('Ws2', (128, 64), True, 'pad'), Entry('Ws3', (64, 32), True, 'pad'),
-                 Entry('Ws4', (32,), True, 'pad')]
+                 Entry('W2', (C, C), True, 'pad'), Entry('Wf1', (Hp, 512), True, 'pad'), Entry('Wf2', (512, C), True, 'pad')]
+        mlp = self.ranking == 'mlp'
+        if mlp:
+            ents += [Entry('Ws1', (C, 128), True, 'pad'), Entry('Ws2', (128, 64), True, 'pad'), Entry('Ws3', (64, 32), True, 'pad'),
+                     Entry('Ws4', (32,), True, 'pad')]
         ents += [Entry('b1', (C,), False, 'zeros'), Entry('b2', (C,), False, 'zeros')]
         for l in range(self.L):
             Ip = C if l == 0 else Hp
@@ -155,8 +163,10 @@ class ParamLayout:
             if rnn_cell == 'gru':    # W_ch directly behind W_gh: the recurrent kernel takes ONE pointer (chameleon_nar.h)
                 ents.append(Entry('rnn%d/Wch' % l, (Hp, Hp), False, 'pad'))
             ents.append(Entry('rnn%d/b' % l, (self.NG * Hp,), False, 'zeros'))
-        ents += [Entry('bf1', (512,), False, 'zeros'), Entry('bf2', (C,), False, 'zeros'), Entry('bs1', (128,), False, 'zeros'),
-                 Entry('bs2', (64,), False, 'zeros'), Entry('bs3', (32,), False, 'zeros'), Entry('bs4', (1,), False, 'zeros')]
+        ents += [Entry('bf1', (512,), False, 'zeros'), Entry('bf2', (C,), False, 'zeros')]
+        if mlp:
+            ents += [Entry('bs1', (128,), False, 'zeros'), Entry('bs2', (64,), False, 'zeros'), Entry('bs3', (32,), False, 'zeros'),
+                     Entry('bs4', (1,), False, 'zeros')]
         off = 0
         self.entries = OrderedDict()
         for e in ents:
@@ -262,7 +272,7 @@ class ParamLayout:
         specs['FC2/bias'] = ((C,), 'zeros', False)
         dims = [C, 128, 64, 32, 1]
         inits = ['variance_scaling', 'variance_scaling', 'variance_scaling', 'lecun_uniform']
-        for i in range(4):
+        for i in range(4 if self.ranking == 'mlp' else 0):
             specs['match%d/kernel' % (i + 1)] = ((dims[i], dims[i + 1]), inits[i], True)
             specs['match%d/bias' % (i + 1)] = ((dims[i + 1],), 'zeros', False)
         return specs
@@ -312,7 +322,7 @@ class ParamLayout:
         for fc in ('FC1', 'FC2'):
             m['main/session_representation/%s/kernel' % fc] = fc + '/kernel'
             m['main/session_representation/%s/bias' % fc] = fc + '/bias'
-        for i in range(1, 5):
+        for i in range(1, 5 if self.ranking == 'mlp' else 1):      # (the cosine head has no variables)
             m['main/recommendations_ranking/cos_sim_positive/matching_dense_layer_%d/kernel' % i] = 'match%d/kernel' % i
             m['main/recommendations_ranking/cos_sim_positive/matching_dense_layer_%d/bias' % i] = 'match%d/bias' % i
         assert set(m.values()) == set(self.logical_specs())
@@ -324,7 +334,7 @@ class ParamLayout:
         a = OrderedDict()
         for v in ('kernel', 'bias'):
             a['main/CAR/CAR_representation/' + v] = 'main/user_personalized_contextual_article_embedding/input/CAR_representation/' + v
-        for i in range(1, 5):
+        for i in range(1, 5 if self.ranking == 'mlp' else 1):
             for v in ('kernel', 'bias'):
                 a['main/recommendations_ranking/matching_dense_layer_%d/%s' % (i, v)] = \
                     'main/recommendations_ranking/cos_sim_positive/matching_dense_layer_%d/%s' % (i, v)
@@ -420,6 +430,8 @@ class ParamLayout:
                 rb[k * Hp:k * Hp + H] = bb[k * H:(k + 1) * H]
         v('Wf1')[:H] = logical['FC1/kernel']; v('bf1')[...] = logical['FC1/bias']
         v('Wf2')[...] = logical['FC2/kernel']; v('bf2')[...] = logical['FC2/bias']
+        if self.ranking != 'mlp':
+            return flat
         for i, (w, bn) in enumerate([('Ws1', 'bs1'), ('Ws2', 'bs2'), ('Ws3', 'bs3')]):
             v(w)[...] = logical['match%d/kernel' % (i + 1)]; v(bn)[...] = logical['match%d/bias' % (i + 1)]
         v('Ws4')[...] = np.asarray(logical['match4/kernel']).reshape(32)
@@ -457,8 +469,9 @@ class ParamLayout:
                 out['rnn/%d/candidate/bias' % l] = rb[2 * Hp:2 * Hp + H].copy()
         out['FC1/kernel'] = v('Wf1')[:H].copy(); out['FC1/bias'] = v('bf1').copy()
         out['FC2/kernel'] = v('Wf2').copy(); out['FC2/bias'] = v('bf2').copy()
-        for i, (w, bn) in enumerate([('Ws1', 'bs1'), ('Ws2', 'bs2'), ('Ws3', 'bs3')]):
-            out['match%d/kernel' % (i + 1)] = v(w).copy(); out['match%d/bias' % (i + 1)] = v(bn).copy()
-        out['match4/kernel'] = v('Ws4').reshape(32, 1).copy(); out['match4/bias'] = v('bs4').reshape(1).copy()
+        if self.ranking == 'mlp':
+            for i, (w, bn) in enumerate([('Ws1', 'bs1'), ('Ws2', 'bs2'), ('Ws3', 'bs3')]):
+                out['match%d/kernel' % (i + 1)] = v(w).copy(); out['match%d/bias' % (i + 1)] = v(bn).copy()
+            out['match4/kernel'] = v('Ws4').reshape(32, 1).copy(); out['match4/bias'] = v('bs4').reshape(1).copy()
         # reorder to the logical spec order
         return OrderedDict((k, out[k]) for k in self.logical_specs())

@@ -154,6 +154,14 @@ class _PinnedRing:
         self.events[self.k] = ev
 
 
+def plane_arms(gemm_dtype, C):
+    """(x3, p3, h2): which plane arithmetic the switches select for gemm_dtype and CAR width C (NARRuntime.__init__ explains each)."""
+    x3 = gemm_dtype == 'f32' and os.environ.get("CHAM_GEMM_X3", "1") == "1"
+    p3 = x3 and os.environ.get("CHAM_GEMM_P3", "1") == "1" and C % 256 == 0
+    h2 = p3 and os.environ.get("CHAM_GEMM_H2", "1") == "1"
+    return x3, p3, h2
+
+
 class NARRuntime:
     """Everything that outlives a single train()/evaluate() call: weights + Adam slots in ONE flat HBM buffer,
     resident article tables (ACE matrix, metadata - re-fed from numpy every step by the reference,
@@ -164,6 +172,10 @@ class NARRuntime:
     def __init__(self, params, device='cuda:0', seed=42, weights=None):
         self.lib = _lib.load()
         self._views = {}
+        _, p3, h2 = plane_arms(params.get('gemm_dtype', 'f32'), params['CAR_embedding_size'])
+        if params.get('recommendations_ranking', 'mlp') == 'cosine' and p3 and not h2:
+            raise ValueError("recommendations_ranking='cosine' is not supported on the three-bf16-plane arm (CHAM_GEMM_H2=0): its backward has "
+                             "no plane-resident form there - use the default two-fp16-plane arm, CHAM_GEMM_P3=0, gemm_dtype 'f32_native' or 'bf16'")
         if not torch.cuda.is_available():
             raise _lib.ChameleonLibError("no ROCm device visible: the NAR step has no CPU path")
         self.device = torch.device(device)
@@ -177,8 +189,12 @@ class NARRuntime:
         self.layout = ParamLayout(params['session_features_config'], acfg, self.n_items, ace.shape[1],
                                   params['CAR_embedding_size'], params['rnn_units'],
                                   params.get('rnn_num_layers', 1), params.get('rnn_cell', 'ugrnn'),
-                                  params.get('internal_features_config'), params.get('max_cardinality_for_ohe', 10))
+                                  params.get('internal_features_config'), params.get('max_cardinality_for_ohe', 10),
+                                  params.get('recommendations_ranking', 'mlp'))
         L = self.layout
+        # ranking head (--recommendations_ranking): 'mlp' = cand (.) pred -> 128 -> 64 -> 32 -> 1, 'cosine' = cos(pred, candidate row), no weights
+        # (csrc/cosine.hip).  The softmax kernels then read cosq [R, 4] with these constants as their last layer
+        self.cosine = L.ranking == 'cosine'
         logical = weights if weights is not None else L.init_logical(seed)
         dev = self.device
         self.flat = torch.from_numpy(L.pack(logical)).to(dev)
@@ -211,17 +227,15 @@ class NARRuntime:
         # 'bf16': BASELINE config 3 (bf16-resident candidate-row matrices, fp32 accumulate).
         if self.gemm_dtype not in ('f32', 'f32_native', 'bf16'):
             raise ValueError("gemm_dtype must be 'f32', 'f32_native' or 'bf16'")
-        self.x3 = self.gemm_dtype == 'f32' and os.environ.get("CHAM_GEMM_X3", "1") == "1"
+        self.x3, self.p3, self.h2 = plane_arms(self.gemm_dtype, self.layout.C)
         # plane-resident CAR GEMMs (csrc/gemm_p3.hip): the candidate rows of Z1 and dZ2 live in HBM as three bf16 planes written by
         # their producers, W2 / W2^T get plane shadows once per step; same six plane products as gemm_x3.hip.  CHAM_GEMM_P3=0: the
         # on-the-fly split for those three GEMMs too (A/B arm).  The only shape gate is C % 256 == 0 below (decided once, here): any other
         # argument the plane kernels reject is an error of this module and raises from check() mid-step - loudly, there is no silent
         # fall-back to another arithmetic
-        self.p3 = self.x3 and os.environ.get("CHAM_GEMM_P3", "1") == "1" and self.layout.C % 256 == 0
         # two-fp16-plane form of those three GEMMs (csrc/gemm_h2.hip, round 4): planes (h, l) x a power-of-two scale derived on the device
         # from a bound of the matrix, THREE plane products instead of six - the kernels were power-limited, so halving the MFMA count is
         # what moves them; same float64-error bar as the six-product form (tests/test_gemm_h2_gpu.py).  CHAM_GEMM_H2=0: the three-bf16-plane arm
-        self.h2 = self.p3 and os.environ.get("CHAM_GEMM_H2", "1") == "1"
         # ... optionally with the candidate-row planes TILE-BLOCKED (round 6; [row tiles of 256][C / 32][256][32], csrc/common.h h2b_index): an
         # LDS-DMA request of the NT forms (16 rows x 32 k) is then 1 KB of whole 128-byte lines instead of sixteen half lines.  Bit-identical
         # results (same pieces, same products).  MEASURED (profiles/r06_notes.md section 2): the NT forms gain 4-5 % (stand-alone 1.41 -> 1.36 and
@@ -296,10 +310,13 @@ class NARRuntime:
         self.b16_dma = self.gemm_dtype == 'bf16' and L.C % 256 == 0
         # ... and the scorer layer-1 dgrad fused with the cand (.) pred / CAR-tanh backward (csrc/dm_fused.hip, MODE 2) where the kernel takes
         # the shape (1 + N in [32, 256] is checked per step)
-        self.dm_fused_b16 = self.gemm_dtype == 'bf16' and L.entries['Ws1'].shape == (L.C, 128) and L.C % 64 == 0
+        self.dm_fused_b16 = self.gemm_dtype == 'bf16' and not self.cosine and L.entries['Ws1'].shape == (L.C, 128) and L.C % 64 == 0
         # plane arms: scorer layer-1 dgrad fused with the cand (.) pred backward (csrc/dm_fused.hip) where the kernel takes the shape; otherwise
         # (and for 1 + N outside [32, 256]) the two separate kernels
-        self.dm_fused = self.p3 and L.entries['Ws1'].shape == (L.C, 128) and L.C % 64 == 0
+        self.dm_fused = self.p3 and not self.cosine and L.entries['Ws1'].shape == (L.C, 128) and L.C % 64 == 0
+        if self.cosine:
+            self.cos_w4 = torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+            self.cos_b4 = torch.zeros(4, dtype=torch.float32, device=dev)
         # The arithmetic of the candidate rows (nar/candidate_rows.py): the arm the switches above select - it allocates its weight planes / shadows
         # and scale records here, as attributes of this runtime - and the fp32 rows every step falls back to that the planes do not take
         self.f32_rows = F32Rows(self)
@@ -571,7 +588,8 @@ class StepPlan:
         Z1, Z2, dZ1, dZ2 over all CAR rows + the scorer activations over the candidate rows + the plane-resident operands of the
         candidate-row CAR GEMMs (Z1 and dZ2 as two fp16 / three bf16 planes), the b2 partial sums and the segment table."""
         rows = B * T * (N + 2)
-        need = 4 * (4 * rows * L.C + 2 * rows * (128 + 64 + 32))        # (the bf16 configuration needs ~5/8 of this)
+        head = 4 + 4 + 2 if getattr(L, 'ranking', 'mlp') == 'cosine' else 2 * (128 + 64 + 32)      # cosine head: cosq + its scratch gradient, rz, the bound buffer
+        need = 4 * (4 * rows * L.C + rows * head)        # (the bf16 configuration needs ~5/8 of this)
         if rt is not None and rt.p3:
             need += (H2Rows if rt.h2 else P3Rows).estimate_bytes(rt, L, B, T, N)
         return need
@@ -660,9 +678,14 @@ class StepPlan:
         # FCs / scorer
         self.FC1, self.dFC1 = f32(BT, 512), f32(BT, 512)
         self.pred, self.dpred = f32(BT, C), f32(BT, C)
-        self.S1, self.dS1 = cand(Rc, 128), cand(Rc, 128)
-        self.S2, self.dS2 = cand(Rc, 64), cand(Rc, 64)
-        self.S3, self.dS3 = cand(Rc, 32), cand(Rc, 32)
+        if rt.cosine:      # cos(pred, candidate row) in column 0 of cosq (the softmax kernels' "S3", K3 = 4; dcosq: their scratch "dS3"), the inverse
+            # norms of the rows and of pred, and the bound buffer |ds| rz of the two-plane backward (csrc/cosine.hip); fp32 in every arm
+            self.cosq, self.dcosq = f32(Rc, 4), f32(Rc, 4)
+            self.rz, self.rp, self.cos_t = f32(Rc), f32(BT), f32((Rc + 3) & ~3)
+        else:
+            self.S1, self.dS1 = cand(Rc, 128), cand(Rc, 128)
+            self.S2, self.dS2 = cand(Rc, 64), cand(Rc, 64)
+            self.S3, self.dS3 = cand(Rc, 32), cand(Rc, 32)
         self.ds = f32(Rc)
         self.logits, self.probs = f32(BT, NC), f32(BT, NC)
         self.nll = f32(BT)
@@ -745,7 +768,7 @@ class NARModuleModel:
                  diversity_reg_factor=0.0,
                  internal_features_config={'recency': True, 'novelty': True, 'article_content_embeddings': True,
                                            'item_clicked_embeddings': True},
-                 eval_cold_start=False, runtime=None, rnn_cell='ugrnn', gemm_dtype='f32'):
+                 eval_cold_start=False, runtime=None, rnn_cell='ugrnn', gemm_dtype='f32', recommendations_ranking='mlp'):
         # log_base / log_1p bases of the recency and novelty features (nar_model.py:28-34, 1071-1075, 1148): launch scalars of the kernels
         for b in (elapsed_days_smooth_log_base, popularity_smooth_log_base):
             if not (b > 0.0) or b == 1.0:
@@ -780,6 +803,7 @@ class NARModuleModel:
                                       content_article_embeddings_matrix=content_article_embeddings_matrix,
                                       articles_metadata=articles_metadata, CAR_embedding_size=CAR_embedding_size,
                                       rnn_units=rnn_units, rnn_num_layers=rnn_num_layers, rnn_cell=rnn_cell, gemm_dtype=gemm_dtype,
+                                      recommendations_ranking=recommendations_ranking,
                                       internal_features_config=internal_features_config,
                                       max_cardinality_for_ohe=max_cardinality_for_ohe,
                                       recent_clicks_buffer_max_size=recent_clicks_buffer_max_size,
@@ -787,6 +811,9 @@ class NARModuleModel:
             if _VARIABLE_STORE is not None:
                 _VARIABLE_STORE['runtime'] = runtime
         self.rt = runtime
+        if recommendations_ranking not in ('mlp', 'cosine'):
+            raise ValueError("recommendations_ranking must be 'mlp' or 'cosine'")
+        self.recommendations_ranking = runtime.layout.ranking      # (the runtime's parameter layout decides: it may outlive this model)
         # state "placeholders" (nar_model.py:195-202): fed by ItemsStateUpdaterHook.before_run
         self.articles_recent_pop_norm = None
         self.pop_recent_items_buffer = None
@@ -1124,10 +1151,15 @@ class NARModuleModel:
         rt.join()
         # scorer: (cand (.) pred) -> 128 -> 64 -> 32 -> 1, softmax(/tau), masked NLL
         _roctx.pop(); _roctx.push("K5 scorer, softmax, loss")
-        arm.scorer_fwd(pl, s)
-        check(getattr(lib, arm.softmax_fwd)(ptr(pl.S3), 32, ptr(p('Ws4')), ptr(p('bs4')), BT, N, float(self.softmax_temperature),
-                                            ptr(pl.mask), ptr(pl.logits), ptr(pl.probs), ptr(pl.nll), self.novelty_reg_factor,
-                                            ptr(neg_ids), ptr(st['pop_norm']), ptr(pl.nov_aux), s), "cham_score_softmax_fwd")
+        if rt.cosine:      # cos(pred, candidate row), then the same kernel: its last-layer dot over (cos, 0, 0, 0) x (1, 0, 0, 0) returns cos (fp32 in every arm)
+            arm.cosine_fwd(pl, s)
+            softmax_fwd, S3, K3, w4, b4 = 'cham_score_softmax_fwd', pl.cosq, 4, rt.cos_w4, rt.cos_b4
+        else:
+            arm.scorer_fwd(pl, s)
+            softmax_fwd, S3, K3, w4, b4 = arm.softmax_fwd, pl.S3, 32, p('Ws4'), p('bs4')
+        check(getattr(lib, softmax_fwd)(ptr(S3), K3, ptr(w4), ptr(b4), BT, N, float(self.softmax_temperature),
+                                        ptr(pl.mask), ptr(pl.logits), ptr(pl.probs), ptr(pl.nll), self.novelty_reg_factor,
+                                        ptr(neg_ids), ptr(st['pop_norm']), ptr(pl.nov_aux), s), "cham_score_softmax_fwd")
         if self.diversity_reg_factor > 0.0:      # + factor * p^T S p into nll, ahead of the loss record below (TRAIN and EVAL)
             sp, e = pl.ensure_diversity()
             check(lib.cham_diversity_fwd(ptr(pl.probs), ptr(d['ln_rows']), ptr(neg_ids), ptr(pl.mask), BT, N, ptr(rt.ace), rt.ace.stride(0),
@@ -1215,26 +1247,32 @@ class NARModuleModel:
             rt.grads[:L.emb_end].zero_()
             e_start = mark()
         # (sum(mask): from the step-scalar record written by this step's forward, or by value)
-        check(getattr(lib, arm.softmax_bwd + ('_dev' if rt.dev_scalars else ''))(
-            ptr(pl.S3), 32, ptr(p('Ws4')), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
-            ptr(rt.scalars) if rt.dev_scalars else d['sum_mask'], ptr(pl.ds), ptr(pl.dS3), self.novelty_reg_factor, ptr(neg_ids),
+        cosine = rt.cosine               # the cosine head: ds is all its backward needs of these two kernels (dcosq is their scratch output)
+        if cosine:
+            softmax_bwd, diversity_bwd, S3, K3, w4, dS3 = 'cham_score_softmax_bwd', 'cham_diversity_bwd', pl.cosq, 4, rt.cos_w4, pl.dcosq
+        else:
+            softmax_bwd, diversity_bwd, S3, K3, w4, dS3 = arm.softmax_bwd, arm.diversity_bwd, pl.S3, 32, p('Ws4'), pl.dS3
+        check(getattr(lib, softmax_bwd + ('_dev' if rt.dev_scalars else ''))(
+            ptr(S3), K3, ptr(w4), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
+            ptr(rt.scalars) if rt.dev_scalars else d['sum_mask'], ptr(pl.ds), ptr(dS3), self.novelty_reg_factor, ptr(neg_ids),
             ptr(self._dev_state['pop_norm']), ptr(pl.logits), ptr(pl.nov_aux), s), "cham_score_softmax_bwd")
         if self.diversity_reg_factor > 0.0:      # ds += the diversity term's logit gradient, dS3 again from it
-            check(getattr(lib, arm.diversity_bwd)(
-                ptr(pl.S3), 32, ptr(p('Ws4')), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
+            check(getattr(lib, diversity_bwd)(
+                ptr(S3), K3, ptr(w4), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
                 ptr(rt.scalars) if rt.dev_scalars else None, 0.0 if rt.dev_scalars else d['sum_mask'], ptr(pl.div_sp), ptr(pl.div_e),
-                self.diversity_reg_factor, ptr(pl.ds), ptr(pl.dS3), s), arm.diversity_bwd)
+                self.diversity_reg_factor, ptr(pl.ds), ptr(dS3), s), diversity_bwd)
         if self._dev_state.get('device'):
             self.articles_recent_pop_norm.note_consumed(d['aci'])      # last read of the state in a TRAIN step
         # scorer dgrad chain on this lane (three short GEMMs); the side lane takes the layer-1 weight gradient FIRST - 65 GFLOP of
         # matrix work that then runs beside the HBM-bound k_mulpred_bwd instead of beside the MFMA-bound CAR dgrad - and the small
         # (HBM-bound, split-K) weight / bias gradients of layers 2-4 after it
-        arm.scorer_dgrad(pl, s)
+        if not cosine:
+            arm.scorer_dgrad(pl, s)
         e_dS1 = mark()     # (starting the side lane only after the next GEMM, to pair its MFMA work with k_mulpred_bwd's HBM work,
         #                      measured 0.26 ms slower: 17.28-17.33 vs 17.01-17.07 ms, A/B in one gpurun call)
         # scorer layer-1 dgrad: through HBM here, unless this step's arm takes it in one kernel with the cand (.) pred backward below
         # (csrc/dm_fused.hip: dM never reaches HBM)
-        if not arm.fused_dz2(pl):
+        if not cosine and not arm.fused_dz2(pl):
             arm.s1_dgrad(pl)
         # Side lane, "critical chain first": with short sessions the CAR GEMMs shrink and the
         # main lane ends up waiting for the clicked-row gradient that comes out of the side lane's FC -> recurrent -> CAR chain (0.4 ms
@@ -1247,11 +1285,14 @@ class NARModuleModel:
         # third lane for the small weight gradients (full batches of the default / six-plane fp32 arithmetic, one recurrent layer of the
         # UGRNN kind: with more layers the per-layer gradients read a buffer the next layer's backward overwrites)
         use_aux = bool(on and rt.wgrad_aux and arm.planes and not w2_main and L.L == 1 and cell == 0 and not L.rnn_stepwise and not drop)
-        with side(e_start, e_dS1):
-            arm.s1_wgrad(pl)
-            if not crit_first:
-                arm.small_wgrads(pl)
-        arm.dz2(pl, s)
+        if cosine:      # no scorer weights: one HBM-bound kernel (+ the bound record of the two-plane arm) takes ds to the gradient at the CAR tanh and dpred
+            arm.cosine_bwd(pl, s)
+        else:
+            with side(e_start, e_dS1):
+                arm.s1_wgrad(pl)
+                if not crit_first:
+                    arm.small_wgrads(pl)
+            arm.dz2(pl, s)
         e_dZ2c = mark()              # dZ2c final + dpred
         # The candidate-row dgrad of CAR layer 2 on the main lane (needs dZ2c only): the largest GEMM of the backward, ENQUEUED BEFORE the
         # side lane's long launch sequence below - in the bf16 configuration the GPU keeps up with the host, and the ~25 launches of the
@@ -1276,7 +1317,7 @@ class NARModuleModel:
                 rt.colsum(pl.dpred, C, BT, C, g('bf2'))
                 rt.gemm(pl.rnn_c if pos is not None else rnn_y(last), pl.dFC1, g('Wf1'), Hp, 512, BT, Hp, 512, 512, transA=1, splits=0)
                 rt.colsum(pl.dFC1, 512, BT, 512, g('bf1'))
-                if crit_first:
+                if crit_first and not cosine:
                     arm.small_wgrads(pl)
                 if rt.dp_early_bucket is not None and not self._accumulating:
                     rt.dp_early_bucket(rt.grads)     # data parallel: [Wf1 .. Ws4] gradients are final - their all-reduce starts now
@@ -1623,6 +1664,8 @@ class GraphedTrainStep:
             return "dropout / cold-start analysis / presampling off"
         if m.diversity_reg_factor > 0.0:
             return "diversity regulariser (its two launches are not part of the captured step)"
+        if rt.cosine:
+            return "cosine ranking head (its launches are not part of the captured step)"
         if self.key is not None and self.shape_key(d) != self.key:
             return "another batch shape than the captured one"
         if self.graph is None:      # capture needs a warm shape: buffers, workspaces, the step-scalar record and the kernels' dynamic-LDS

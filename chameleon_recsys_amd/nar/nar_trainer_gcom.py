@@ -92,6 +92,12 @@ def define_flags():
       "(nar_model.py:1317), 'gru' / 'lstm' = its commented-out GRUCell and LSTMCell alternatives (:1315-1316).  All take --rnn_units up to "
       "1024: the fused time-loop kernels up to 512 (ugrnn) / 384 (gru), one launch sequence per time step beyond - and for the lstm at "
       "every width")
+    a('--recommendations_ranking', default='mlp', choices=['mlp', 'cosine'],
+      help="ranking head: 'mlp' = the reference's running code, cand (.) pred -> 128 -> 64 -> 32 -> 1 (nar_model.py:444-517); 'cosine' = the "
+           "DSSM-style head its comments at nar_model.py:435-437 describe (\"l2-norm to be able to compute cosine similarity\"): the cosine "
+           "between the predicted session embedding and each candidate's contextual article embedding, then the same softmax with "
+           "--softmax_temperature as the smoothing factor.  The cosine head has no matching_dense_layer variables; checkpoints of the two "
+           "modes do not cross-load")
     a('--gemm_dtype', default='f32', choices=['f32', 'f32_native', 'bf16'],
       help="f32: fp32 operands and fp32-grade error, wide GEMMs as six bf16-plane products on the bf16 matrix cores (caveats: an INFINITE "
            "operand yields NaN where fp32 yields +-inf - behind a tanh layer the native path saturates to a finite +-1 instead - and "
@@ -205,7 +211,8 @@ def nar_module_model_fn(features, labels, mode, params):
                            metrics_top_n=eval_metrics_top_n, plot_histograms=params['save_histograms'],
                            novelty_reg_factor=params['novelty_reg_factor'], diversity_reg_factor=params['diversity_reg_factor'],
                            internal_features_config=internal_features_config, eval_cold_start=params['eval_cold_start'],
-                           rnn_cell=params.get('rnn_cell', 'ugrnn'), gemm_dtype=params.get('gemm_dtype', 'f32'))
+                           rnn_cell=params.get('rnn_cell', 'ugrnn'), gemm_dtype=params.get('gemm_dtype', 'f32'),
+                           recommendations_ranking=params.get('recommendations_ranking', 'mlp'))
     state = params.get('clicked_items_state') or clicked_items_state
     metrics_log = params.get('eval_sessions_metrics_log', eval_sessions_metrics_log)
     eval_metrics = {'hitrate_at_n': StreamingMean(), 'mrr_at_n': StreamingMean()} if mode == ModeKeys.EVAL else {}
@@ -237,7 +244,7 @@ def build_estimator(model_dir, content_article_embeddings_matrix, articles_metad
         'recent_clicks_for_normalization': FLAGS.recent_clicks_for_normalization,
         'eval_metrics_top_n': FLAGS.eval_metrics_top_n, 'CAR_embedding_size': FLAGS.CAR_embedding_size,
         'rnn_units': FLAGS.rnn_units, 'rnn_num_layers': 1,   # the reference never forwards --rnn_num_layers (:252-275)
-        'rnn_cell': FLAGS.rnn_cell, 'gemm_dtype': FLAGS.gemm_dtype,
+        'rnn_cell': FLAGS.rnn_cell, 'gemm_dtype': FLAGS.gemm_dtype, 'recommendations_ranking': FLAGS.recommendations_ranking,
         'train_total_negative_samples': FLAGS.train_total_negative_samples,
         'train_negative_samples_from_buffer': FLAGS.train_negative_samples_from_buffer,
         'eval_total_negative_samples': FLAGS.eval_total_negative_samples,

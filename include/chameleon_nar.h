@@ -488,7 +488,7 @@ int cham_score_softmax_bwd(const float* S3, int K3, const float* w4, const float
  *   cham_diversity_bwd[_b16]: behind cham_score_softmax_bwd[_b16][_dev] of the same S3 storage:
  *     ds[row] += factor * mask / (tau * sum_mask) * 2 p_c (sp_c - e) and dS3[row,k] = ds[row] * w4[k] * leaky'(S3[row,k]) rewritten from the
  *     updated ds in that kernel's operation order.  sum(mask) comes from the step-scalar record `scalars` when it is not NULL, else from
- *     `sum_mask` by value - the same fp32 expression either way.  K3 == 32. */
+ *     `sum_mask` by value - the same fp32 expression either way.  K3 == 32, or 4 for the cosine head below. */
 int cham_diversity_fwd(const float* probs, const int64_t* label_ids, const int64_t* neg_ids, const uint8_t* mask, int BT, int N,
                        const float* ace, int ld_ace, int D, int64_t n_items, float diversity_reg_factor, float* sp, float* e, float* nll,
                        void* stream);
@@ -498,6 +498,33 @@ int cham_diversity_bwd(const float* S3, int K3, const float* w4, const float* pr
 int cham_diversity_bwd_b16(const void* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N, float tau,
                            const void* scalars, float sum_mask, const float* sp, const float* e, float diversity_reg_factor, float* ds,
                            void* dS3, void* stream);
+
+/* Cosine-similarity ranking head (--recommendations_ranking cosine; csrc/cosine.hip): the DSSM-style formulation the comments of
+ * nar_model.py:435-437 refer to.  logit_c = cos(pred[bt], Z2c[bt (N+1) + c]), both vectors l2-normalised as tf.nn.l2_normalize does:
+ * inv(x) = 1 / sqrt(max(sum x^2, 1e-12)).  The head has no weights; softmax, NLL, novelty and diversity are the kernels above with
+ * K3 = 4 (the fp32 entry points in every arithmetic), S3 = cosq, w4 = (1, 0, 0, 0), b4 = 0: logits == cosq[:, 0] bit for bit.
+ *   fwd[_b16]: Z2c = the R = BT (1 + N) candidate rows of the CAR tanh output, fp32 or bf16, row stride ldz elements (% 4 == 0);
+ *     pred [BT, C].  Writes cosq [R, 4] = (cos, 0, 0, 0), rz [R] and rp [BT], the inverse norms.  A vector whose sum of squares is below
+ *     1e-12 gets EXACTLY 1e6, every other at most the fp32 number below 1e6: the backward reads the clamp off the value.
+ *   bound: t [ceil4(R)] = |ds_r| rz_r (0 in the padding); max t bounds every |dZ2pre| (|p^_k - cos z^_k| <= sin of the angle <= 1), so
+ *     cham_h2_scale_absmax(t, ceil4(R), NULL, 0, rec) gives the scale record of the two-plane form.
+ *   bwd / bwd_h2 / bwd_b16: from ds [R] (cham_score_softmax_bwd, + cham_diversity_bwd) the gradient at the two tanh pre-activations,
+ *     dZ2pre_ck = ds_c rz_c (p^_k - cos_c z^_ck) (1 - z_ck^2) as fp32 rows [R, C] / two fp16 planes x the scale of scale_rec / bf16 rows, and
+ *     dpred_pre_k = (sum_c ds_c rp (z^_ck - cos_c p^_k)) (1 - p_k^2) [BT, C]; the projection term of a clamped vector is dropped (the
+ *     constant 1e6 carries no gradient).  b2part [BT, C] (may be NULL) = the column sums of the click's rows as stored.  Rows of a masked
+ *     click (mask == 0) are written as zeros.  1 + N <= 5461.  Fixed summation order, no atomics. */
+int cham_cosine_fwd(const float* Z2c, long long ldz, const float* pred, int C, int BT, int N, float* cosq, float* rz, float* rp,
+                    void* stream);
+int cham_cosine_fwd_b16(const void* Z2c, long long ldz, const float* pred, int C, int BT, int N, float* cosq, float* rz, float* rp,
+                        void* stream);
+int cham_cosine_bound(const float* ds, const float* rz, size_t rows, float* t, void* stream);
+int cham_cosine_bwd(const float* Z2c, const float* pred, const float* ds, const float* rz, const float* rp, const float* cosq,
+                    const uint8_t* mask, int C, int BT, int N, float* dZ2pre, float* dpred_pre, float* b2part, void* stream);
+int cham_cosine_bwd_h2(const float* Z2c, const float* pred, const float* ds, const float* rz, const float* rp, const float* cosq,
+                       const uint8_t* mask, int C, int BT, int N, void* dZ2p, long long plane_stride, const void* scale_rec,
+                       float* dpred_pre, float* b2part, void* stream);
+int cham_cosine_bwd_b16(const void* Z2c, const float* pred, const float* ds, const float* rz, const float* rp, const float* cosq,
+                        const uint8_t* mask, int C, int BT, int N, void* dZ2pre, float* dpred_pre, float* b2part, void* stream);
 
 /* evaluation: rank_items_by_predicted_prob, nar_model.py:777-794 (tf.nn.top_k over 1+N: descending, lowest index wins
  * ties).  pred_ids/pred_probs [BT, 1+N]; label_rank[bt] = 0-based rank of the positive, -1 for padded clicks - the input of
