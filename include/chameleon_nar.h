@@ -611,6 +611,38 @@ size_t cham_eval_coverage_workspace_bytes(int64_t n_items);
 int cham_eval_coverage_count(const uint8_t* rec_map, const uint8_t* clk_map, int64_t n_items, void* workspace, size_t workspace_bytes,
                              int64_t* counts, void* stream);
 
+/* --- ACR module: the CNN article encoder (reference acr_module/acr/acr_model.py:83-87 embedding_lookup of the constant word-embedding
+ * matrix, :272-289 cnn_feature_extractor, :196-198 weighted sparse softmax cross-entropy, :171 argmax), csrc/acr.hip.
+ *   conv_k[b,t,f] = relu(bias_k[f] + sum_{j<k} sum_e table[tokens[b,t+j], e] W_k[j,e,f]),  t = 0 .. L-k     ("valid")
+ *   pool[b, s F + f] = max_t conv_{k_s}[b,t,f],  argmax[b, s F + f] = the SMALLEST t that attains it
+ * tokens int32 [B, L] (ids in [0, V); id 0 = <PAD> is an ordinary row); table fp32 [V, ldE], 16-byte aligned, ldE % 4 == 0, ldE >= E, any
+ * E >= 1 (columns [E, ldE) are never used), 64-bit row offsets; sizes = n_sizes (1..8) HOST ints in [1, 16]; W / bias = HOST arrays of
+ * n_sizes device pointers, W[s] = [k_s, E, F] contiguous (tf.layers.conv1d's kernel), bias[s] = [F]; pool [B, ldP] (ldP >= n_sizes F; columns
+ * beyond n_sizes F are not written), argmax int32 [B, n_sizes F].  Neither the gathered input nor the conv output reaches memory: rows
+ * t0 .. t0+31+kmax-1 of an article are staged in LDS once for all sizes (E <= 320; wider rows in passes of 320 columns), products on
+ * v_mfma_f32_32x32x2_f32; (max, argmax) partials per 32-position tile go through `workspace` (cham_acr_conv_pool_workspace_bytes) and are
+ * reduced in tile order: no atomics, two runs are bit-identical, bit-equal windows give bit-equal values.  L < max(k) (the reference yields
+ * an empty max), or any argument outside the above: -EINVAL, nothing launched or written.
+ * Backward (the table is constant: no dx), g[b,c] = dpool[b,c] where pool[b,c] > 0, else 0:
+ *   dW_k[(j,e), f] = sum_b g[b,f] table[tokens[b, argmax_k[b,f] + j], e],   dbias_k[f] = sum_b g[b,f]
+ * written (not accumulated) to dW[s] / dbias[s] (HOST arrays of device pointers into the flat gradient buffer); b ascending, no atomics. */
+size_t cham_acr_conv_pool_workspace_bytes(int B, int L, const int* sizes, int n_sizes, int F);
+int cham_acr_conv_pool_fwd(const int32_t* tokens, int B, int L, const float* table, long long V, int E, long long ldE, const int* sizes,
+                           int n_sizes, int F, const float* const* W, const float* const* bias, float* pool, int ldP, int32_t* argmax,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int cham_acr_conv_pool_bwd(const int32_t* tokens, int B, int L, const float* table, long long V, int E, long long ldE, const int* sizes,
+                           int n_sizes, int F, const float* dpool, const float* pool, int ldP, const int32_t* argmax, float* const* dW,
+                           float* const* dbias, void* stream);
+/* one multiclass label head: logits [B, ld] of true width C (columns [C, ld) are never read), labels int32 [B] in [0, C), class_weights [C]
+ * or NULL.  loss[0] = sum_b w_b ce_b / #{b : w_b != 0} (tf.losses SUM_BY_NONZERO_WEIGHTS; 0 when every weight is 0; the mean without
+ * weights); dlogits [B, ld] (or NULL) = d loss / d logits with that denominator folded in, columns [C, ld) written 0; pred [B] = argmax
+ * with the first index on ties; row_workspace [B] floats. */
+int cham_acr_softmax_xent(const float* logits, int ld, int B, int C, const int32_t* labels, const float* class_weights, float* loss,
+                          float* dlogits, int32_t* pred, float* row_workspace, void* stream);
+/* x = relu(x) in place; dy *= act'(y) in place from the saved POST-activation y (act 0 = ReLU, 1 = tanh).  n % 4 == 0, 16-byte aligned. */
+int cham_acr_relu(float* x, size_t n, void* stream);
+int cham_acr_act_bwd(float* dy, const float* y, size_t n, int act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
