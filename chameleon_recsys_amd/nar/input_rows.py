@@ -114,6 +114,35 @@ class FeatureRows:
             check(lib.cham_norm_stats_from_rows(pl.rec_raw[a:].data_ptr(), pl.nov_raw[a:].data_ptr(), pl.w_rows[a:].data_ptr(), b - a,
                                                 pl.stats[g].data_ptr(), s), "cham_norm_stats_from_rows")
 
+    def norm_stats_first_batch_of_shard(self, pl, d, st, neg_slot, s):
+        """The very first batch when the call is a ROW SHARD of it (micro-batch, data-parallel rank): the population is the GLOBAL batch's
+        non-pad ids, not the shard's - the whole-batch step normalises every row with the statistics of all clicked ids, all positives and
+        all sampled negatives (nar_model.py:1078-1084, 1168-1181), and every shard must use the same ones.  Every shard holds what that
+        takes: the global ids d['aci'] [Bg, T + 1], time stamps and session lengths d['g_seq_len'] - the valid positions are t < length, as
+        upload_batch masks them; the clicked id of position t is aci[:, t], its positive aci[:, t + 1], the session's last one the label in
+        column T - and `neg_slot`, the pool slots of the GLOBAL batch's negatives (NARModuleModel._whole_batch_neg_slots).  Same rows in
+        the same order and the same launches as norm_stats() on the whole batch's valid positions, into pl.stats.  Once per training run:
+        scratch tensors, one host synchronisation (the boolean compaction)."""
+        rt, lib, T, pmax = self.rt, self.rt.lib, d['T'], pl.pmax
+        aci, ets, lens = d['aci'], d['g_event_ts'], d['g_seq_len'].long().clamp(0, T)
+        valid = torch.arange(T, device=aci.device)[None, :] < lens[:, None]
+        nxt = aci[:, 1:].clone()
+        has = lens > 0
+        nxt[has, lens[has] - 1] = aci[has, T]
+        ids_c, ts_c, ids_p = aci[:, :T][valid], ets[valid], nxt[valid]
+        P = ids_c.numel()
+        ids = torch.cat([ids_c, ids_p, pl.pool[:pmax], torch.zeros(1, dtype=torch.int64, device=aci.device)])
+        ref_ts = torch.cat([ts_c, ets.max().reshape(1).expand(P + pmax + 1)])
+        R = 2 * P + pmax + 1
+        rec, nov, w = (torch.empty(R, dtype=torch.float32, device=aci.device) for _ in range(3))
+        check(lib.cham_item_dynamic_raw(ptr(ids), ptr(ref_ts), R, ptr(rt.created), ptr(st['pop_norm']), ptr(rec), ptr(nov), s),
+              "cham_item_dynamic_raw")
+        check(lib.cham_row_weights(ptr(ids), 2 * P, ptr(neg_slot), neg_slot.numel(), pmax, ptr(pl.pool), ptr(w), w[2 * P:].data_ptr(), s),
+              "cham_row_weights")
+        for g, (a, b) in enumerate([(0, P), (P, 2 * P), (2 * P, R)]):
+            check(lib.cham_norm_stats_from_rows(rec[a:].data_ptr(), nov[a:].data_ptr(), w[a:].data_ptr(), b - a, pl.stats[g].data_ptr(), s),
+                  "cham_norm_stats_from_rows")
+
     def assemble(self, pl, d, s):      # raw + scaled / centred rows: user context (one per position), items (one per row of the item row set)
         rt, lib, L, p, BT = self.rt, self.rt.lib, self.rt.layout, self.rt.p, pl.P
         pl.cat = d['cat']

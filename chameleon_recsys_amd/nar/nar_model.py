@@ -911,6 +911,8 @@ class NARModuleModel:
         pos = np.flatnonzero(mrows).astype(np.int32)
         P = int(pos.shape[0])
         host = dict(g_event_ts=g_ets, aci=aci, item_clicked=item_clicked, label_next=label_next, event_ts=ets, seq_len=seq_len)
+        if global_features is not None:      # lengths of the GLOBAL batch's sessions (a row shard's first-batch statistics: FeatureRows)
+            host['g_seq_len'] = np.minimum(np.maximum(g_ssz - 1, 0), g_T).astype(np.int32)
         compacted = self.rt.compact and 0 < P < B * T
         if compacted:
             host.update(pos=pos, ic_rows=item_clicked.reshape(-1)[pos], ln_rows=label_next.reshape(-1)[pos], ets_rows=ets.reshape(-1)[pos],
@@ -921,6 +923,8 @@ class NARModuleModel:
         d.update(self._h2d(host))
         if not compacted:
             d.update(ic_rows=d['item_clicked'].view(-1), ln_rows=d['label_next'].view(-1), ets_rows=d['event_ts'].view(-1))
+        if global_features is None:
+            d['g_seq_len'] = d['seq_len']
         return d
 
     def _h2d(self, host):
@@ -968,20 +972,36 @@ class NARModuleModel:
             ring.end(up if up is not None else main)
         return out
 
-    def _neg_sample(self, pl, d, step, k, stream, which=None):
+    def _neg_sample(self, pl, d, step, k, stream, which=None, out=None, rows=None):
         """K0 negative sampling (nar_model.py:265-276) of batch d with key `step` into the plan's sampler-output set k.  which = 0 / 1: the key
-        is the .step / .step_next field of the runtime's step-scalar record (device) instead of the argument."""
-        rt, st, o = self.rt, self._dev_state, pl._samp[k]
+        is the .step / .step_next field of the runtime's step-scalar record (device) instead of the argument.  out, rows: other outputs than
+        set k's, for the global rows [rows[0], rows[0] + rows[1]) instead of this call's (_whole_batch_neg_slots)."""
+        rt, st, o = self.rt, self._dev_state, pl._samp[k] if out is None else out
+        row_begin, row_count = (d['row_begin'], d['B']) if rows is None else rows
         if which is not None:
             check(rt.lib.cham_neg_sample_dev(ptr(d['aci']), d['Bg'], d['T'] + 1, ptr(st['buffer']), st['buffer'].numel(),
-                                             rt.tf_random_seed, ptr(rt.scalars), which, d['row_begin'], d['B'], self.negative_samples,
+                                             rt.tf_random_seed, ptr(rt.scalars), which, row_begin, row_count, self.negative_samples,
                                              self.negative_sample_from_buffer, ptr(o['neg_ids']), ptr(o['neg_slot']), ptr(o['pool']),
                                              ptr(o['canon']), ptr(o['meta']), ptr(pl.sampler_ws), pl.ws_bytes, stream), "cham_neg_sample_dev")
             return
         check(rt.lib.cham_neg_sample(ptr(d['aci']), d['Bg'], d['T'] + 1, ptr(st['buffer']), st['buffer'].numel(),
-                                     rt.tf_random_seed, step, d['row_begin'], d['B'], self.negative_samples,
+                                     rt.tf_random_seed, step, row_begin, row_count, self.negative_samples,
                                      self.negative_sample_from_buffer, ptr(o['neg_ids']), ptr(o['neg_slot']), ptr(o['pool']),
                                      ptr(o['canon']), ptr(o['meta']), ptr(pl.sampler_ws), pl.ws_bytes, stream), "cham_neg_sample")
+
+    def _whole_batch_neg_slots(self, pl, d, step, stream, which=None):
+        """Pool slots [Bg, T, N] of the negatives of EVERY row of the global batch, for a call that is a row shard of it (the first batch's
+        statistics, _forward): the sampler once more with rows [0, Bg) into scratch outputs (it is keyed by the global row, so these are the
+        negatives each shard draws for its own rows).  Once per training run: 12 bytes per global negative of scratch (ids + slots; about
+        200 MB at 4096 sessions x 20 x 200), freed on return of the step.  The draw rebuilds the pool in the plan's sampler workspace: that
+        workspace is sized by the global batch and nothing reads it after a sampler call has returned its outputs, so this call's own
+        negatives (drawn before, on the same stream) are not affected."""
+        Bg, T, N, dev = d['Bg'], d['T'], self.negative_samples, self.rt.device
+        out = dict(neg_ids=torch.empty(Bg, T, N, dtype=torch.int64, device=dev), neg_slot=torch.empty(Bg, T, N, dtype=torch.int32, device=dev),
+                   pool=torch.empty(pl.pmax, dtype=torch.int64, device=dev), canon=torch.empty(pl.pmax, dtype=torch.int32, device=dev),
+                   meta=torch.empty(4, dtype=torch.int32, device=dev))
+        self._neg_sample(pl, d, step, pl._samp_cur, stream, which=which, out=out, rows=(0, Bg))
+        return out['neg_slot']
 
     def presample(self, d):
         """Draw the negatives of the NEXT training step now.  Sampling depends on the recent-clicks state and the batch's ids,
@@ -1096,7 +1116,12 @@ class NARModuleModel:
             else:
                 fr.group_rows(pl, s)
         fr.dynamic_raw(pl, st, s)
-        fr.norm_stats(pl, d, st, s)
+        if st['n_last'] == 0 and (d['Bg'] > B or d['row_begin'] > 0):
+            # the very first batch, and this call is a row shard of it: the statistics of the GLOBAL batch's rows, as the whole-batch step
+            # takes them - the negatives of every global row drawn once more (the sampler is keyed by the global row) for their multiplicities
+            fr.norm_stats_first_batch_of_shard(pl, d, st, self._whole_batch_neg_slots(pl, d, step, s, which=0 if dsc else None), s)
+        else:
+            fr.norm_stats(pl, d, st, s)
         fr.assemble(pl, d, s)
         if shadows_ev is not None:
             torch.cuda.current_stream().wait_event(shadows_ev)
@@ -1454,8 +1479,10 @@ class NARModuleModel:
     def train_step_microbatched(self, features, labels, micro_sessions, global_features=None, global_labels=None, row_begin=0):
         """One optimizer step over the batch processed as row shards of ``micro_sessions`` sessions (activations of the
         B*T*(1+N) candidate rows bounded by the shard; BASELINE config 5 = 4096 sessions x 200 negatives).  Every shard sees
-        the GLOBAL ids (pool, max timestamp, sum(mask), sampler keyed by the global row), gradients accumulate, ONE Adam.
-        Same result as train_step on the whole batch up to fp32 summation order (tests: shard-sum / micro-batch parity)."""
+        the GLOBAL ids (pool, max timestamp, sum(mask), sampler keyed by the global row; on the very first batch also the normalisation
+        statistics of the global batch's rows), gradients accumulate, ONE Adam.
+        Same result as train_step on the whole batch up to fp32 summation order (tests/test_shard_paths_gpu.py: every model variant,
+        warm and empty recent-clicks state; bf16: up to the bf16 rounding of the per-shard dU / dV sums)."""
         from .parallel import slice_batch
         rt = self.rt
         gf = features if global_features is None else global_features
