@@ -30,7 +30,7 @@
 //     nar_model.py:478-495 fused into the scorer's first layer and its wgrad).
 //   * epilogue (compile-time specialised): bias + {none, leaky_relu(0.2), tanh}; or multiply by act'(saved output)
 //     for dgrad; optional accumulate.  Split-K (grid.y) writes raw partials, reduced in fixed order (deterministic).
-#include "gemm_shared.h"
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 // One operand tile [BF x BK].  Offsets are tile-window-local bytes, computed once; per K tile only the k-validity
@@ -347,156 +347,38 @@ extern "C" void cham_gemm_launch_counts(long long* out16, int reset) {
     for (int i = 0; i < 16; ++i) { if (out16) out16[i] = g_tile_launches[i]; if (reset) g_tile_launches[i] = 0; }
 }
 
-template <int BM, int BN, int WM, int WN, int BK, bool AK, bool BKC, int EPI, bool BF16>
-static int launch_epi(GemmParams& p, hipStream_t st) {
-    g_tile_launches[14] = EPI; g_tile_launches[15] = p.splits;
-    size_t smem;
-    const void* kern;
-    if (BF16) {
-        smem = (size_t)2 * (BM + BN) * (BK + 8) * 2;
-        // the row-broadcast scale only ever accompanies the scorer's first layer (bias+leaky, NN) and its wgrad (TN; split-K, or
-        // plain when the reduction is too short to split: a batch with a handful of valid positions)
-        constexpr bool RSI = (EPI == 1 && AK && !BKC) || ((EPI == 6 || EPI == 0) && !AK && !BKC);
-        if (p.rs != nullptr && !RSI) return -CHAM_ERR_ARG;
-        if (RSI && p.rs != nullptr) {
-            auto k = gemm_bf16_kernel<BM, BN, WM, WN, BK, AK, BKC, EPI, RSI>;
-            CHAM_SET_DYNAMIC_LDS(k, (int)smem);
-            hipLaunchKernelGGL(k, dim3(p.nbm * p.nbn, p.splits, 1), dim3(WM * WN * 64), smem, st, p);
-            CHAM_CHECK_LAUNCH();
-            return CHAM_OK;
-        }
-        kern = reinterpret_cast<const void*>(gemm_bf16_kernel<BM, BN, WM, WN, BK, AK, BKC, EPI, false>);
-    } else {
-        using LA = TileLoader<BM, BK, AK, WM * WN * 64>;
-        using LB = TileLoader<BN, BK, BKC, WM * WN * 64>;
-        smem = (size_t)2 * BK * (LA::LD + LB::LD) * sizeof(float);
-        constexpr bool RSI = (EPI == 1 && AK && !BKC) || ((EPI == 6 || EPI == 0) && !AK && !BKC);
-        if (p.rs != nullptr && !RSI) return -CHAM_ERR_ARG;
-        if (RSI && p.rs != nullptr) {
-            auto k = gemm_f32_kernel<BM, BN, WM, WN, BK, AK, BKC, EPI, RSI>;
-            CHAM_SET_DYNAMIC_LDS(k, (int)smem);
-            hipLaunchKernelGGL(k, dim3(p.nbm * p.nbn, p.splits, 1), dim3(WM * WN * 64), smem, st, p);
-            CHAM_CHECK_LAUNCH();
-            return CHAM_OK;
-        }
-        kern = reinterpret_cast<const void*>(gemm_f32_kernel<BM, BN, WM, WN, BK, AK, BKC, EPI, false>);
-    }
-    CHAM_SET_DYNAMIC_LDS(kern, (int)smem);
-    dim3 grid(p.nbm * p.nbn, p.splits, 1);
-    if (BF16) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, BK, AK, BKC, EPI, false>), grid, dim3(WM * WN * 64), smem, st, p);
-    else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, BK, AK, BKC, EPI, false>), grid, dim3(WM * WN * 64), smem, st, p);
-    CHAM_CHECK_LAUNCH();
-    return CHAM_OK;
-}
-
-template <int BM, int BN, int WM, int WN, int BK, bool AK, bool BKC, bool BF16 = false>
+// One tile instance, fp32 (BK = 16) or staged as bf16 (BK = 32): tile counts, epilogue and row-scale rules in gemm_tile.h's ladder.
+template <int BM, int BN, int WM, int WN, bool AK, bool BKC, bool BF16>
 static int launch_cfg(GemmParams& p, hipStream_t st) {
-    p.nbm = (p.M + BM - 1) / BM;
-    p.nbn = (p.N + BN - 1) / BN;
-    // Epilogues are instantiated for the layouts that use them (a third of the library's code size otherwise):
-    //   NN (forward)  plain | bias | bias + leaky | bias + tanh        NT (dgrad)  plain / accumulate | x leaky'(dref) | x tanh'(dref)
-    //   TN (wgrad)    plain / accumulate | split-K partial
-    // gemm_plan never plans K-splits for NN / NT; the other combinations return -EINVAL.
-    constexpr bool NN = AK && !BKC, NT = AK && BKC, TN = !AK && !BKC;
-    if (p.splits > 1) {
-        if constexpr (TN) {
-            p.xcd_split = (p.splits % 8 == 0) ? 1 : 0;
-            const int rc = launch_epi<BM, BN, WM, WN, BK, AK, BKC, 6, BF16>(p, st);
-            if (rc != CHAM_OK) return rc;
-            launch_splitk_reduce(p, st);
-            CHAM_CHECK_LAUNCH();
-            return CHAM_OK;
-        } else {
-            return -CHAM_ERR_ARG;
-        }
-    }
-    if (p.dref) {
-        if (p.bias || p.act != ACT_NONE) return -CHAM_ERR_ARG;
-        if constexpr (NT) {
-            if (p.dact == ACT_LEAKY) return launch_epi<BM, BN, WM, WN, BK, AK, BKC, 3, BF16>(p, st);
-            if (p.dact == ACT_TANH) return launch_epi<BM, BN, WM, WN, BK, AK, BKC, 4, BF16>(p, st);
-        }
-        return -CHAM_ERR_ARG;
-    }
-    if (p.bias || p.act != ACT_NONE) {
-        if (!p.bias || p.accumulate) return -CHAM_ERR_ARG;       // every activated layer of the model has a bias
-        if constexpr (NN) {
-            if (p.act == ACT_LEAKY) return launch_epi<BM, BN, WM, WN, BK, AK, BKC, 1, BF16>(p, st);
-            if (p.act == ACT_TANH) return launch_epi<BM, BN, WM, WN, BK, AK, BKC, 2, BF16>(p, st);
-            return launch_epi<BM, BN, WM, WN, BK, AK, BKC, 5, BF16>(p, st);
-        }
-        return -CHAM_ERR_ARG;
-    }
-    return launch_epi<BM, BN, WM, WN, BK, AK, BKC, 0, BF16>(p, st);
+    constexpr int BK = BF16 ? 32 : 16, NTH = WM * WN * 64;
+    constexpr size_t smem = BF16 ? (size_t)2 * (BM + BN) * (BK + 8) * 2
+                                 : (size_t)2 * BK * (TileLoader<BM, BK, AK, NTH>::LD + TileLoader<BN, BK, BKC, NTH>::LD) * sizeof(float);
+    return tile_ladder_f32<BM, BN, AK, BKC>(p, g_tile_launches + 14, st, [&](auto epi, auto rs) {
+        constexpr int EPI = decltype(epi)::value;
+        constexpr bool RS = decltype(rs)::value;
+        // (a plain `if`, as it has always been: the library also carries the fp32 kernels at BK = 32 and the bf16 ones at BK = 16, which
+        // nothing launches - dropping them is a change of the kernel set and not part of this ladder)
+        if (BF16) return tile_launch<gemm_bf16_kernel<BM, BN, WM, WN, BK, AK, BKC, EPI, RS>>(p, EPI, NTH, smem, g_tile_launches + 14, st);
+        return tile_launch<gemm_f32_kernel<BM, BN, WM, WN, BK, AK, BKC, EPI, RS>>(p, EPI, NTH, smem, g_tile_launches + 14, st);
+    });
 }
 
 static int g_variant = -1;     // -1 = automatic
 extern "C" void cham_gemm_set_variant(int v) { g_variant = v; }
-template <bool AK, bool BKC>
+// tile_plan's tile index -> instance.  Measured on MI355X at the CAR shapes (profiles/r01_gemm_variants.md): NN 256x128 126-130 TFLOP/s;
+// NT (dgrad) and TN (wgrad, long K) prefer the 256x256 tile (123 / 133 TFLOP/s), which the bf16 kernels do not have; other tile shapes were
+// measured and dropped (profiles/r01_notes.md items 3 and 9).  The tile counter moves before the ladder can reject the call.
+template <bool AK, bool BKC, bool BF16>
 static int launch_by_shape(GemmParams& p, hipStream_t st) {
-    if (p.N > 64) {
-        // default: 256x128 tile / 8 waves for large outputs, 128x128 / 4 waves when the grid would otherwise be too
-        // small to fill 256 CUs
-        // measured on MI355X at the CAR shapes (profiles/r01_gemm_variants.md): NN 256x128 126-130 TFLOP/s; NT (dgrad) and
-        // TN (wgrad, long K) prefer the 256x256 tile (123 / 133 TFLOP/s)
-        // the largest tile whose grid still gives every one of the 256 CUs a workgroup (a 4 864-row GEMM on 256x256 tiles is 76
-        // workgroups: 70 % of the chip idle)
-        auto grid = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * p.splits; };
-        int v = ((long)p.M * p.N >= (1L << 20)) ? 2 : 0;
-        if (v == 2 && (!AK || BKC) && p.K >= 512 && p.M >= 1024 && p.N >= 512) v = 4;
-        if (v == 4 && grid(256, 256) < 256) v = 2;       // ... demoted while the grid does not cover the chip
-        if (v == 2 && grid(256, 128) < 256) v = 0;
-        if (g_variant >= 0) v = g_variant;
-        switch (v) {      // (other tile shapes were measured and dropped: profiles/r01_notes.md items 3 and 9)
-            case 2: ++g_tile_launches[1]; return launch_cfg<256, 128, 4, 2, 16, AK, BKC>(p, st);
-            case 4: ++g_tile_launches[2]; return launch_cfg<256, 256, 4, 2, 16, AK, BKC>(p, st);
-            default: ++g_tile_launches[0]; return launch_cfg<128, 128, 2, 2, 16, AK, BKC>(p, st);
-        }
+    const int t = BF16 ? tile_plan::tile_bf16(p.M, p.N, p.splits, g_variant) : tile_plan::tile_f32(p.M, p.N, p.K, p.splits, AK, BKC, g_variant);
+    ++g_tile_launches[(BF16 ? 8 : 0) + t];
+    switch (t) {
+        case 1: return launch_cfg<256, 128, 4, 2, AK, BKC, BF16>(p, st);
+        case 2: if constexpr (!BF16) return launch_cfg<256, 256, 4, 2, AK, BKC, BF16>(p, st); else return -CHAM_ERR_ARG;
+        case 3: return launch_cfg<256, 64, 4, 1, AK, BKC, BF16>(p, st);
+        case 4: return launch_cfg<256, 32, 4, 1, AK, BKC, BF16>(p, st);
+        default: return launch_cfg<128, 128, 2, 2, AK, BKC, BF16>(p, st);
     }
-    if (p.N > 32) { ++g_tile_launches[3]; return launch_cfg<256, 64, 4, 1, 16, AK, BKC>(p, st); }
-    ++g_tile_launches[4];
-    return launch_cfg<256, 32, 4, 1, 16, AK, BKC>(p, st);
-}
-
-template <bool AK, bool BKC>
-static int launch_by_shape_bf16(GemmParams& p, hipStream_t st) {
-    if (p.N > 64) {
-        bool big = (long)p.M * p.N >= (1L << 20) && (long)((p.M + 255) / 256) * ((p.N + 127) / 128) * p.splits >= 256;
-        if (g_variant >= 0) big = g_variant >= 2;
-        if (big) { ++g_tile_launches[8 + 1]; return launch_cfg<256, 128, 4, 2, 32, AK, BKC, true>(p, st); }
-        ++g_tile_launches[8 + 0];
-        return launch_cfg<128, 128, 2, 2, 32, AK, BKC, true>(p, st);
-    }
-    if (p.N > 32) { ++g_tile_launches[8 + 3]; return launch_cfg<256, 64, 4, 1, 32, AK, BKC, true>(p, st); }
-    ++g_tile_launches[8 + 4];
-    return launch_cfg<256, 32, 4, 1, 32, AK, BKC, true>(p, st);
-}
-
-static int gemm_dispatch(int precision, const float* A, int lda, int transA, const float* B, int ldb, int transB,
-                         float* C, int ldc, int M, int N, int K, const float* bias, int act, const float* dref, int ldr, int dact,
-                         const float* rowscale, int ldrs, int rs_div, int accumulate, float* workspace, size_t workspace_bytes,
-                         int splits_hint, void* stream);
-
-extern "C" int cham_gemm_f32(const float* A, int lda, int transA, const float* B, int ldb, int transB,
-                             float* C, int ldc, int M, int N, int K,
-                             const float* bias, int act,
-                             const float* dref, int ldr, int dact,
-                             const float* rowscale, int ldrs, int rs_div,
-                             int accumulate, float* workspace, size_t workspace_bytes, int splits_hint,
-                             void* stream) {
-    return gemm_dispatch(0, A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, rowscale, ldrs, rs_div,
-                         accumulate, workspace, workspace_bytes, splits_hint, stream);
-}
-// same contract, operands rounded to bf16 on the fly, fp32 accumulate / epilogue / output
-extern "C" int cham_gemm_bf16(const float* A, int lda, int transA, const float* B, int ldb, int transB,
-                              float* C, int ldc, int M, int N, int K,
-                              const float* bias, int act,
-                              const float* dref, int ldr, int dact,
-                              const float* rowscale, int ldrs, int rs_div,
-                              int accumulate, float* workspace, size_t workspace_bytes, int splits_hint,
-                              void* stream) {
-    return gemm_dispatch(1, A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, rowscale, ldrs, rs_div,
-                         accumulate, workspace, workspace_bytes, splits_hint, stream);
 }
 
 // ================================================================================================================================
@@ -621,42 +503,50 @@ static int launch_tn_small(GemmParams& p, hipStream_t st) {
     return CHAM_OK;
 }
 
-static int gemm_dispatch(int precision, const float* A, int lda, int transA, const float* B, int ldb, int transB,
+template <bool BF16>
+static int gemm_dispatch(const float* A, int lda, int transA, const float* B, int ldb, int transB,
+                         float* C, int ldc, int M, int N, int K, const float* bias, int act, const float* dref, int ldr, int dact,
+                         const float* rowscale, int ldrs, int rs_div, int accumulate, float* workspace, size_t workspace_bytes,
+                         int splits_hint, void* stream) {
+    GemmParams p;
+    const int rc = gemm_plan(p, A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, rowscale, ldrs, rs_div,
+                             accumulate, workspace, workspace_bytes, splits_hint);
+    if (rc != CHAM_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // small-output weight gradient (see gemm_tn_small_kernel): plain TN, M <= 128, a reduction long enough to matter; with operands
+    // beyond its 32-bit offsets it is left to the tile kernels
+    if (!BF16 && transA && !transB && M <= 128 && K >= 512 && !bias && act == ACT_NONE && !dref && !rowscale && tn_small_enabled() &&
+        (size_t)K * (lda > ldb ? lda : ldb) * 4 < 0x7FFFFFF0ull) {
+        // a wave owns at most 2 x 2 tiles of 32 x 32 (64 accumulator registers: the kernel stays under the ~160 VGPRs that are free beside the
+        // plane GEMMs' two waves per SIMD); more row tiles go to blockIdx.z (their workgroups re-read the B block: a few MB through L2)
+        const int mt = (M + 31) / 32;
+        if (N <= 32) return mt == 1 ? launch_tn_small<1, 1>(p, st) : launch_tn_small<2, 1>(p, st);
+        return mt == 1 ? launch_tn_small<1, 2>(p, st) : launch_tn_small<2, 2>(p, st);
+    }
+    if (!transA && !transB) return launch_by_shape<true, false, BF16>(p, st);
+    if (!transA && transB) return launch_by_shape<true, true, BF16>(p, st);
+    if (transA && !transB) return launch_by_shape<false, false, BF16>(p, st);
+    return -CHAM_ERR_ARG;                                // TT never occurs on this path
+}
+
+extern "C" int cham_gemm_f32(const float* A, int lda, int transA, const float* B, int ldb, int transB,
                              float* C, int ldc, int M, int N, int K,
                              const float* bias, int act,
                              const float* dref, int ldr, int dact,
                              const float* rowscale, int ldrs, int rs_div,
                              int accumulate, float* workspace, size_t workspace_bytes, int splits_hint,
                              void* stream) {
-    GemmParams p;
-    // small-output weight gradient (see gemm_tn_small_kernel): plain TN, M <= 128, a reduction long enough to matter
-    if (precision == 0 && transA && !transB && M <= 128 && K >= 512 && !bias && act == ACT_NONE && !dref && !rowscale && tn_small_enabled()) {
-        const int rc0 = gemm_plan(p, A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, rowscale, ldrs, rs_div,
-                                  accumulate, workspace, workspace_bytes, splits_hint);
-        if (rc0 != CHAM_OK) return rc0;
-        hipStream_t st0 = (hipStream_t)stream;
-        // a wave owns at most 2 x 2 tiles of 32 x 32 (64 accumulator registers: the kernel stays under the ~160 VGPRs that are free beside the
-        // plane GEMMs' two waves per SIMD); more row tiles go to blockIdx.z (their workgroups re-read the B block: a few MB through L2)
-        if ((size_t)K * (lda > ldb ? lda : ldb) * 4 >= 0x7FFFFFF0ull) { /* 32-bit operand offsets: leave it to the tile kernels below */ }
-        else {
-            const int mt = (M + 31) / 32;
-            if (N <= 32) return mt == 1 ? launch_tn_small<1, 1>(p, st0) : launch_tn_small<2, 1>(p, st0);
-            return mt == 1 ? launch_tn_small<1, 2>(p, st0) : launch_tn_small<2, 2>(p, st0);
-        }
-    }
-    const int rc = gemm_plan(p, A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, rowscale, ldrs, rs_div,
-                             accumulate, workspace, workspace_bytes, splits_hint);
-    if (rc != CHAM_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (precision == 1) {
-        if (!transA && !transB) return launch_by_shape_bf16<true, false>(p, st);
-        if (!transA && transB) return launch_by_shape_bf16<true, true>(p, st);
-        if (transA && !transB) return launch_by_shape_bf16<false, false>(p, st);
-        return -CHAM_ERR_ARG;
-    }
-    if (!transA && !transB) return launch_by_shape<true, false>(p, st);
-    if (!transA && transB) return launch_by_shape<true, true>(p, st);
-    if (transA && !transB) return launch_by_shape<false, false>(p, st);
-    return -CHAM_ERR_ARG;                                // TT never occurs on this path
+    return gemm_dispatch<false>(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, rowscale, ldrs, rs_div,
+                                accumulate, workspace, workspace_bytes, splits_hint, stream);
 }
-
+// same contract, operands rounded to bf16 on the fly, fp32 accumulate / epilogue / output
+extern "C" int cham_gemm_bf16(const float* A, int lda, int transA, const float* B, int ldb, int transB,
+                              float* C, int ldc, int M, int N, int K,
+                              const float* bias, int act,
+                              const float* dref, int ldr, int dact,
+                              const float* rowscale, int ldrs, int rs_div,
+                              int accumulate, float* workspace, size_t workspace_bytes, int splits_hint,
+                              void* stream) {
+    return gemm_dispatch<true>(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, rowscale, ldrs, rs_div,
+                               accumulate, workspace, workspace_bytes, splits_hint, stream);
+}

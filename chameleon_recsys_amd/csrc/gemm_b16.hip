@@ -20,8 +20,7 @@
 //     and the fragments - 8 consecutive k of one row per lane - are gathered by the LDS transpose read ds_read_b64_tr_b16
 //     (two per fragment; layout verified on the device: tests/probe/tr_probe.hip).
 //   * buffer-descriptor windows, XCD-aware tile swizzle and the one-K-split-per-XCD placement of gemm_shared.h.
-#define GEMM_SHARED_NO_SPLITK_REDUCE          /* gemm_b16_splitk_reduce[_wide] below */
-#include "gemm_shared.h"
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 struct B16Params {
@@ -233,58 +232,6 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void gemm_b16_kernel(B16Params 
     }
 }
 
-// fixed-order reduction of the split-K partials
-__global__ __launch_bounds__(256) void gemm_b16_splitk_reduce(const float* __restrict__ partial, int splits, int M, int N,
-                                                              float* __restrict__ C, int ldc, int accumulate) {
-    const size_t n4 = (size_t)M * N / 4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int s = 0; s < splits; ++s) {
-            const float4 x = reinterpret_cast<const float4*>(partial + (size_t)s * M * N)[i];
-            v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
-        }
-        const size_t e = i * 4;
-        const int row = (int)(e / N), col = (int)(e % N);
-        float4* c = reinterpret_cast<float4*>(C + (size_t)row * ldc + col);
-        if (accumulate) { const float4 o = *c; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-        *c = v;
-    }
-}
-
-// Small outputs with MANY splits (the scorer's weight gradients: a [1024, 128] output has 128 K-splits and the form above walks them with
-// 128 workgroups of dependent loads - 0.32 ms per launch, the largest kernel-time item of the bf16 step in rocprofv3's summary): 16 threads
-// share one group of four columns, thread g sums the splits g, g + 16, ..., the sixteen sums are added in ascending g through LDS (as
-// gemm_shared.h's gemm_splitk_reduce_wide) - a fixed order.
-__global__ __launch_bounds__(256) void gemm_b16_splitk_reduce_wide(const float* __restrict__ partial, int splits, int M, int N,
-                                                                   float* __restrict__ C, int ldc, int accumulate) {
-    __shared__ float4 red[256];
-    const size_t n4 = (size_t)M * N / 4;
-    const int o = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const size_t i = (size_t)blockIdx.x * 16 + o;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < n4) {
-        const float4* src = reinterpret_cast<const float4*>(partial) + i;
-        int s = g;
-        for (; s + 48 < splits; s += 64) {
-            const float4 x0 = src[(size_t)s * n4], x1 = src[(size_t)(s + 16) * n4], x2 = src[(size_t)(s + 32) * n4], x3 = src[(size_t)(s + 48) * n4];
-            v.x += x0.x; v.y += x0.y; v.z += x0.z; v.w += x0.w;
-            v.x += x1.x; v.y += x1.y; v.z += x1.z; v.w += x1.w;
-            v.x += x2.x; v.y += x2.y; v.z += x2.z; v.w += x2.w;
-            v.x += x3.x; v.y += x3.y; v.z += x3.z; v.w += x3.w;
-        }
-        for (; s < splits; s += 16) { const float4 x = src[(size_t)s * n4]; v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w; }
-    }
-    red[threadIdx.x] = v;
-    __syncthreads();
-    if (g != 0 || i >= n4) return;
-    for (int q = 1; q < 16; ++q) { const float4 x = red[q * 16 + o]; v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w; }
-    const size_t e = i * 4;
-    const int row = (int)(e / N), col = (int)(e % N);
-    float4* c = reinterpret_cast<float4*>(C + (size_t)row * ldc + col);
-    if (accumulate) { const float4 old = *c; v.x += old.x; v.y += old.y; v.z += old.z; v.w += old.w; }
-    *c = v;
-}
-
 // [0] 128x128, [1] 256x128 / 8 waves, [2] 256x128 / 4 waves, [3] 256x64, [4] 256x32; of the LAST launch: [5] fp32 output, [6] epilogue
 // variant, [7] K-splits (test / bench aid, not thread-safe)
 static long long g_b16_launches[8];
@@ -294,80 +241,44 @@ extern "C" void cham_gemm_b16_launch_counts(long long* out8, int reset) {
     for (int i = 0; i < 8; ++i) { if (out8) out8[i] = g_b16_launches[i]; if (reset && i < 5) g_b16_launches[i] = 0; }
 }
 
-template <int BM, int BN, int WM, int WN, int BK, int MINW, bool AK, bool BKC, int EPI, bool OUTF32>
-static int b16_launch_epi(B16Params& p, hipStream_t st) {
-    using LA = Stage16<BM, BK, AK, WM * WN * 64>;
-    using LB = Stage16<BN, BK, BKC, WM * WN * 64>;
-    constexpr int ASZ = AK ? BM * LA::LD : BK * LA::LD, BSZ = BKC ? BN * LB::LD : BK * LB::LD;
-    const size_t smem = (size_t)2 * (ASZ + BSZ) * 2;
-    g_b16_launches[5] = OUTF32; g_b16_launches[6] = EPI; g_b16_launches[7] = p.splits;
-    auto k = gemm_b16_kernel<BM, BN, WM, WN, BK, MINW, AK, BKC, EPI, OUTF32>;
-    CHAM_SET_DYNAMIC_LDS(k, (int)smem);
-    hipLaunchKernelGGL(k, dim3(p.nbm * p.nbn, p.splits, 1), dim3(WM * WN * 64), smem, st, p);
-    CHAM_CHECK_LAUNCH();
-    return CHAM_OK;
-}
-
-template <int BM, int BN, int WM, int WN, int BK, int MINW, bool AK, bool BKC>
+// One tile instance (BK = 32): tile_plan::epilogue_b16 picks EPI and what the kernel writes, gemm_tile.h's ladder launches it and, after a
+// split-K partial launch, the shared fixed-order reduction - wide up to 65536 float4 groups of output here (a [1024, 256] gradient).
+template <int BM, int BN, int WM, int WN, bool AK, bool BKC>
 static int b16_launch_cfg(B16Params& p, int act, int dact, int out_f32, hipStream_t st) {
-    p.nbm = (p.M + BM - 1) / BM;
-    p.nbn = (p.N + BN - 1) / BN;
-    if (!AK) {                                           // TN (wgrad): fp32 out, plain or split-K
-        if (p.bias || act != ACT_NONE || p.dref || !out_f32) return -CHAM_ERR_ARG;
-        if (p.splits > 1) {
-            p.xcd_split = (p.splits % 8 == 0 ) ? 1 : 0;
-            const int rc = b16_launch_epi<BM, BN, WM, WN, BK, MINW, AK, BKC, 6, true>(p, st);
-            if (rc != CHAM_OK) return rc;
-            const size_t n4 = (size_t)p.M * p.N / 4;
-            if (n4 <= 65536 && p.splits >= 32) {
-                hipLaunchKernelGGL(gemm_b16_splitk_reduce_wide, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, p.partial, p.splits, p.M, p.N,
-                                   reinterpret_cast<float*>(p.C), p.ldc, p.accumulate);
-            } else {
-                int blocks = (int)((n4 + 255) / 256);
-                if (blocks > 4096) blocks = 4096;
-                hipLaunchKernelGGL(gemm_b16_splitk_reduce, dim3(blocks), dim3(256), 0, st, p.partial, p.splits, p.M, p.N,
-                                   reinterpret_cast<float*>(p.C), p.ldc, p.accumulate);
-            }
-            CHAM_CHECK_LAUNCH();
-            return CHAM_OK;
+    constexpr int BK = 32, NTH = WM * WN * 64;
+    using LA = Stage16<BM, BK, AK, NTH>;
+    using LB = Stage16<BN, BK, BKC, NTH>;
+    constexpr size_t smem = (size_t)2 * ((AK ? BM * LA::LD : BK * LA::LD) + (BKC ? BN * LB::LD : BK * LB::LD)) * 2;
+    bool f32;
+    const int epi = tile_plan::epilogue_b16(!AK, p.bias != nullptr, act, p.dref != nullptr, dact, p.accumulate != 0, p.splits > 1, out_f32 != 0, f32);
+    auto kernel = [&](auto e, auto f) -> int {
+        constexpr int EPI = decltype(e)::value;
+        constexpr bool OUTF32 = decltype(f)::value;
+        if constexpr (tile_plan::instance_b16(EPI, OUTF32)) {
+            g_b16_launches[5] = OUTF32;
+            return tile_launch<gemm_b16_kernel<BM, BN, WM, WN, BK, 1, AK, BKC, EPI, OUTF32>>(p, EPI, NTH, smem, g_b16_launches + 6, st);
+        } else {
+            return -CHAM_ERR_ARG;
         }
-        return b16_launch_epi<BM, BN, WM, WN, BK, MINW, AK, BKC, 0, true>(p, st);
-    }
-    if (p.splits > 1 || p.accumulate) return -CHAM_ERR_ARG;
-    // NT epilogues the bf16 configuration uses (bf16 out): plain, + bias -> leaky | tanh, x leaky'(dref); plain also with fp32 out.
-    // (tanh' dgrads and bias-only layers of the model run on fp32-resident operands: cham_gemm_bf16.)
-    if (p.dref) {
-        if (p.bias || act != ACT_NONE || out_f32 || dact != ACT_LEAKY) return -CHAM_ERR_ARG;
-        return b16_launch_epi<BM, BN, WM, WN, BK, MINW, AK, BKC, 3, false>(p, st);
-    }
-    if (p.bias) {
-        if (out_f32) return -CHAM_ERR_ARG;
-        if (act == ACT_LEAKY) return b16_launch_epi<BM, BN, WM, WN, BK, MINW, AK, BKC, 1, false>(p, st);
-        if (act == ACT_TANH) return b16_launch_epi<BM, BN, WM, WN, BK, MINW, AK, BKC, 2, false>(p, st);
-        return -CHAM_ERR_ARG;
-    }
-    if (act != ACT_NONE) return -CHAM_ERR_ARG;
-    return out_f32 ? b16_launch_epi<BM, BN, WM, WN, BK, MINW, AK, BKC, 0, true>(p, st) : b16_launch_epi<BM, BN, WM, WN, BK, MINW, AK, BKC, 0, false>(p, st);
+    };
+    return tile_ladder<BM, BN>(p, epi, 65536, st, [&](auto e) { return f32 ? kernel(e, std::true_type()) : kernel(e, std::false_type()); });
 }
 
+// tile_plan's tile index -> instance: 1 = 256x128 / 8 waves (64x64 per wave), 2 = 256x128 / 4 waves (128x64 per wave: half the LDS fragment
+// bytes per MFMA; the NT epilogues push that instance past 256 VGPRs and it loses, 425 vs 653 TFLOP/s).  The tile counter moves before the
+// ladder can reject the call.
 template <bool AK, bool BKC>
 static int b16_by_shape(B16Params& p, int act, int dact, int out_f32, hipStream_t st) {
-    if (p.N > 64) {
-        // 256x128 while the grid still covers the 256 CUs; g_b16_variant: 0 = 128x128, 1 = 256x128 / 8 waves (64x64 per wave),
-        // 2 = 256x128 / 4 waves (128x64 per wave: half the LDS fragment bytes per MFMA)
-        int v = ((long)((p.M + 255) / 256) * ((p.N + 127) / 128) * p.splits >= 256) ? 1 : 0;
-        // TN (split-K partial epilogue: 208 VGPRs, two workgroups per CU) is faster on the 4-wave 128x64-per-wave instance (W2 wgrad
-        // 785 vs 707 TFLOP/s stand-alone); the NT epilogues push that instance past 256 VGPRs and it loses (425 vs 653)
-        if (v == 1 && !AK && p.splits > 1) v = 2;
-        if (g_b16_variant >= 0) v = g_b16_variant;
-        ++g_b16_launches[v < 3 ? v : 2];
-        if (v == 1) return b16_launch_cfg<256, 128, 4, 2, 32, 1, AK, BKC>(p, act, dact, out_f32, st);
-        if (v == 2) return b16_launch_cfg<256, 128, 2, 2, 32, 1, AK, BKC>(p, act, dact, out_f32, st);
-        return b16_launch_cfg<128, 128, 2, 2, 32, 1, AK, BKC>(p, act, dact, out_f32, st);
+    int counter;
+    const int t = tile_plan::tile_b16(p.M, p.N, p.splits, !AK, g_b16_variant, counter);
+    ++g_b16_launches[counter];
+    switch (t) {
+        case 1: return b16_launch_cfg<256, 128, 4, 2, AK, BKC>(p, act, dact, out_f32, st);
+        case 2: return b16_launch_cfg<256, 128, 2, 2, AK, BKC>(p, act, dact, out_f32, st);
+        case 3: return b16_launch_cfg<256, 64, 4, 1, AK, BKC>(p, act, dact, out_f32, st);
+        case 4: return b16_launch_cfg<256, 32, 4, 1, AK, BKC>(p, act, dact, out_f32, st);
+        default: return b16_launch_cfg<128, 128, 2, 2, AK, BKC>(p, act, dact, out_f32, st);
     }
-    if (p.N > 32) { ++g_b16_launches[3]; return b16_launch_cfg<256, 64, 4, 1, 32, 1, AK, BKC>(p, act, dact, out_f32, st); }
-    ++g_b16_launches[4];
-    return b16_launch_cfg<256, 32, 4, 1, 32, 1, AK, BKC>(p, act, dact, out_f32, st);
 }
 
 // C[M,N] (+)= epi(op(A) op(B)) with bf16 operands resident in HBM.
@@ -379,39 +290,18 @@ static int b16_by_shape(B16Params& p, int act, int dact, int out_f32, hipStream_
 extern "C" int cham_gemm_b16(const void* A, int lda, int transA, const void* B, int ldb, int transB, void* C, int ldc, int out_f32,
                              int M, int N, int K, const float* bias, int act, const void* dref, int ldr, int dact, int accumulate,
                              float* workspace, size_t workspace_bytes, int splits_hint, void* stream) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return -CHAM_ERR_ARG;
-    if ((lda & 7) || (ldb & 7) || (N & 3) || (ldc & 3) || (dref && (ldr & 3))) return -CHAM_ERR_ARG;
-    if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)dref | (uintptr_t)bias) & 15) return -CHAM_ERR_ARG;
-    const bool nt = !transA && transB, tn = transA && !transB;
-    if (!nt && !tn) return -CHAM_ERR_ARG;
-    if (nt && (K & 7)) return -CHAM_ERR_ARG;
-    if (tn && ((M & 7) || (N & 7))) return -CHAM_ERR_ARG;
-    if (lda < (tn ? M : K) || ldb < (tn ? N : K) || ldc < N || (dref && ldr < N)) return -CHAM_ERR_ARG;      // leading dimension < the extent it strides over
-    if ((size_t)lda * 2 * 256 >= WINDOW_BYTES || (size_t)ldb * 2 * 256 >= WINDOW_BYTES || (size_t)ldc * 4 * 256 >= WINDOW_BYTES ||
-        (size_t)ldr * 2 * 256 >= WINDOW_BYTES)
-        return -CHAM_ERR_ARG;
+    const tile_plan::Args a = {A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, nullptr, 0, 1,
+                               accumulate, workspace, workspace_bytes, splits_hint};
+    tile_plan::SplitPlan plan;
+    const int rc = tile_plan::plan_b16(a, plan);
+    if (rc != CHAM_OK) return rc;
     B16Params p;
     p.A = reinterpret_cast<const __bf16*>(A); p.B = reinterpret_cast<const __bf16*>(B); p.C = C;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.bias = bias; p.dref = reinterpret_cast<const __bf16*>(dref); p.ldr = ldr;
     p.accumulate = accumulate; p.partial = workspace; p.xcd_split = 0;
-    int splits = 1;
-    if (tn && splits_hint != 1 && workspace) {
-        const int bm = (N > 64) ? 256 : 256, bn = (N > 64) ? 128 : (N > 32 ? 64 : 32);
-        const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-        long want = splits_hint > 1 ? splits_hint : (tiles >= 384 ? 1 : (512 + tiles - 1) / tiles);
-        const long maxk = (K + 511) / 512;                 // at least 512 reduction steps per split
-        if (want > maxk) want = maxk;
-        const long maxw = (long)(workspace_bytes / ((size_t)M * N * sizeof(float)));
-        if (want > maxw) want = maxw;
-        if (want >= 8) want = want / 8 * 8;                // whole K-splits per XCD
-        if (want > 1) splits = (int)want;
-    }
-    int kchunk = (K + splits - 1) / splits;
-    kchunk = ((kchunk + 31) / 32) * 32;
-    p.kchunk = kchunk;
-    p.splits = (K + kchunk - 1) / kchunk;
+    p.kchunk = plan.kchunk; p.splits = plan.splits;
     hipStream_t st = (hipStream_t)stream;
-    if (nt) return b16_by_shape<true, true>(p, act, dact, out_f32, st);
+    if (transB) return b16_by_shape<true, true>(p, act, dact, out_f32, st);
     return b16_by_shape<false, false>(p, act, dact, out_f32, st);
 }

@@ -1,14 +1,20 @@
 // Pieces shared by the GEMM translation units (gemm.hip: native fp32 MFMA and the on-the-fly bf16 variant; gemm_x3.hip: fp32 through
 // three bf16 planes; gemm_b16.hip: bf16-resident operands; gemm_dma.h: the LDS-DMA core of gemm_p3.hip and gemm_h2.hip): the parameter
-// block, tile windows, the workgroup -> tile map, the common epilogue, the bf16 staging loader and the split-K reduction.
+// block, tile windows, the workgroup -> tile map, the common epilogue, the bf16 staging loader and the ONE pair of split-K reduction kernels
+// with its launcher.  The host-side decisions of the three register-staged families (argument checks, split-K plan, epilogue, tile) live in
+// gemm_tile_plan.h (plain C++, tested without a GPU); gemm_plan at the bottom fills GemmParams from them, and gemm_tile.h holds the
+// families' one launch helper and epilogue ladder.
 #pragma once
 #include "common.h"
+#include "gemm_tile_plan.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 #define OOB_OFF 0x80000000u          // > every window size below: loads return 0, stores are dropped
 #define WINDOW_BYTES 0x7FFFF000
+static_assert(tile_plan::kOk == CHAM_OK && tile_plan::kErrArg == CHAM_ERR_ARG && tile_plan::kWindowBytes == WINDOW_BYTES, "gemm_tile_plan.h constants");
+static_assert(tile_plan::kActNone == ACT_NONE && tile_plan::kActLeaky == ACT_LEAKY && tile_plan::kActTanh == ACT_TANH, "gemm_tile_plan.h constants");
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_window(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, WINDOW_BYTES, 0x00020000);
@@ -291,9 +297,6 @@ struct TileLoaderBF {
 };
 
 
-// (GEMM_SHARED_NO_SPLITK_REDUCE: gemm_b16.hip keeps reducers of its own - another wide / plain threshold, i.e. another summation order for
-// some shapes - and a `static __global__` kernel is emitted whether or not the file launches it)
-#ifndef GEMM_SHARED_NO_SPLITK_REDUCE
 // fixed-order reduction of split-K partials (+ the generic epilogue).  Four consecutive columns per thread (16-byte loads of every
 // partial slab, four slabs in flight), the slabs added in ascending split order exactly as the scalar form did (bit-identical sums).
 // Round 2's one-element-per-thread form with a 64-bit divide per element cost 1.1 ms per step over its ten launches.
@@ -369,9 +372,11 @@ static __global__ __launch_bounds__(256) void gemm_splitk_reduce_wide(GemmParams
     if (p.accumulate) { v.x += c[0]; v.y += c[1]; v.z += c[2]; v.w += c[3]; }
     c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w;
 }
-static inline void launch_splitk_reduce(const GemmParams& p, hipStream_t st) {
+// wide_max_n4: up to this many float4 groups of output (and from 32 splits on) the wide form runs - the threshold decides the summation
+// order of a shape, so every caller keeps the one it was tuned and tested with: 32768, cham_gemm_b16 65536
+static inline void launch_splitk_reduce(const GemmParams& p, hipStream_t st, size_t wide_max_n4 = 32768) {
     const size_t n4 = (size_t)p.M * p.N / 4;
-    if (n4 <= 32768 && p.splits >= 32) {
+    if (n4 <= wide_max_n4 && p.splits >= 32) {
         hipLaunchKernelGGL(gemm_splitk_reduce_wide, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, p);
     } else {
         int blocks = (int)((n4 + 255) / 256);
@@ -379,56 +384,22 @@ static inline void launch_splitk_reduce(const GemmParams& p, hipStream_t st) {
         hipLaunchKernelGGL(gemm_splitk_reduce, dim3(blocks), dim3(256), 0, st, p);
     }
 }
-#endif
 
 
-// Argument checks + the split-K plan shared by every precision (host side).
+// Argument checks + the split-K plan of the fp32-storage families (host side): tile_plan::plan_f32 decides, this fills the parameter block.
 static inline int gemm_plan(GemmParams& p, const float* A, int lda, int transA, const float* B, int ldb, int transB,
                             float* C, int ldc, int M, int N, int K, const float* bias, int act, const float* dref, int ldr, int dact,
                             const float* rowscale, int ldrs, int rs_div, int accumulate, float* workspace, size_t workspace_bytes,
                             int splits_hint) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K < 0) return -CHAM_ERR_ARG;
-    if ((lda & 3) || (ldb & 3)) return -CHAM_ERR_ARG;
-    // contiguous extents must be float4 multiples (model dims are padded on the host side)
-    if (!transA && (K & 3)) return -CHAM_ERR_ARG;        // A[M,K] row-major, k contiguous
-    if (transA && (M & 3)) return -CHAM_ERR_ARG;         // A stored [K,M]
-    if (!transB && (N & 3)) return -CHAM_ERR_ARG;        // B[K,N] row-major
-    if (transB && (K & 3)) return -CHAM_ERR_ARG;         // B stored [N,K]
-    if (rowscale && ((ldrs & 3) || rs_div <= 0)) return -CHAM_ERR_ARG;
-    // a leading dimension is never smaller than the extent it strides over (with ldc < N the rows of C would overwrite each other)
-    if (lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N || (dref && ldr < N) || (rowscale && ldrs < (transA ? M : K)))
-        return -CHAM_ERR_ARG;
-    // tile windows address 2^31 bytes with 32-bit offsets: a 256-row (or 32-k-row) slab of any operand must fit
-    if ((size_t)lda * 4 * 256 >= WINDOW_BYTES || (size_t)ldb * 4 * 256 >= WINDOW_BYTES || (size_t)ldc * 4 * 256 >= WINDOW_BYTES ||
-        (size_t)ldr * 4 * 256 >= WINDOW_BYTES)
-        return -CHAM_ERR_ARG;
-    if (rowscale && (size_t)((transA ? K : M) / (rs_div > 0 ? rs_div : 1) + 1) * ldrs * 4 >= WINDOW_BYTES) return -CHAM_ERR_ARG;
+    const tile_plan::Args a = {A, lda, transA, B, ldb, transB, C, ldc, M, N, K, bias, act, dref, ldr, dact, rowscale, ldrs, rs_div,
+                               accumulate, workspace, workspace_bytes, splits_hint};
+    tile_plan::SplitPlan plan;
+    const int rc = tile_plan::plan_f32(a, plan);
+    if (rc != CHAM_OK) return rc;
     p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.bias = bias; p.act = act; p.dref = dref; p.ldr = ldr; p.dact = dact;
     p.rs = rowscale; p.ldrs = ldrs; p.rs_div = rs_div > 0 ? rs_div : 1;
     p.accumulate = accumulate; p.partial = workspace; p.xcd_split = 0; p.sa = nullptr; p.sb = nullptr;
-    int splits = 1;
-    // the split-K reductions (gemm_splitk_reduce / _wide) walk the output in float4 groups of one row and read the bias 16 bytes at a
-    // time: an output width that is not a multiple of four (only possible with transB) or a misaligned bias takes the unsplit kernel
-    const bool reduce_ok = (N & 3) == 0 && (!bias || (reinterpret_cast<size_t>(bias) & 15) == 0);
-    // K-splits are a weight-gradient device (TN: long reduction, small output); the NN / NT kernels have no split-K instances
-    if (splits_hint != 1 && workspace && reduce_ok && transA && !transB) {
-        // long-reduction / small-output shapes (wgrad): fill >= ~1024 workgroups
-        const int bm = (N > 64) ? (((long)M * N >= (1L << 20)) ? 256 : 128) : 256, bn = (N > 64) ? 128 : (N > 32 ? 64 : 32);
-        const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-        long want = splits_hint > 1 ? splits_hint : (tiles >= 384 ? 1 : (512 + tiles - 1) / tiles);
-        const long maxk = (K + 255) / 256;               // at least 256 reduction steps per split
-        if (want > maxk) want = maxk;
-        const long maxw = (long)(workspace_bytes / ((size_t)M * N * sizeof(float)));
-        if (want > maxw) want = maxw;
-        if (want > 1) splits = (int)want;
-    }
-    p.splits = splits;
-    int kchunk = (K + splits - 1) / splits;
-    kchunk = ((kchunk + 63) / 64) * 64;                  // multiple of every BK (and of gemm_x3.hip's four-tile unrolled body)
-    if (kchunk == 0) kchunk = 64;
-    p.kchunk = kchunk;
-    p.splits = (K + kchunk - 1) / kchunk;
-    if (p.splits < 1) p.splits = 1;
+    p.kchunk = plan.kchunk; p.splits = plan.splits;
     return CHAM_OK;
 }

@@ -24,7 +24,7 @@
 #ifndef X3_ABL
 #define X3_ABL 0
 #endif
-#include "gemm_shared.h"
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 
@@ -420,82 +420,28 @@ extern "C" void cham_gemm_f32x3_launch_counts(long long* out8, int reset) {
     for (int i = 0; i < 8; ++i) { if (out8) out8[i] = g_x3_launches[i]; if (reset) g_x3_launches[i] = 0; }
 }
 
-template <int BM, int BN, int WM, int WN, int BK, bool AK, bool BKC, int EPI, int NP>
-static int x3_launch_epi(GemmParams& p, hipStream_t st) {
-    g_x3_launches[6] = EPI; g_x3_launches[7] = p.splits;
-    constexpr size_t smem = (size_t)2 * NP * (StageX3<BM, 16, AK, WM * WN * 64, false>::PLANE + StageX3<BN, 16, BKC, WM * WN * 64, false>::PLANE) * 2;
-    constexpr bool RSI = (EPI == 1 && AK && !BKC) || ((EPI == 6 || EPI == 0) && !AK && !BKC);      // as in gemm.hip
-    if (p.rs != nullptr && !RSI) return -CHAM_ERR_ARG;
-    const dim3 grid(p.nbm * p.nbn, p.splits, 1), block(WM * WN * 64);
-    if (RSI && p.rs != nullptr) {
-        auto k = gemm_x3_kernel<BM, BN, WM, WN, AK, BKC, EPI, RSI, NP>;
-        CHAM_SET_DYNAMIC_LDS(k, (int)smem);
-        hipLaunchKernelGGL(k, grid, block, smem, st, p);
-        CHAM_CHECK_LAUNCH();
-        return CHAM_OK;
-    }
-    auto k = gemm_x3_kernel<BM, BN, WM, WN, AK, BKC, EPI, false, NP>;
-    CHAM_SET_DYNAMIC_LDS(k, (int)smem);
-    hipLaunchKernelGGL(k, grid, block, smem, st, p);
-    CHAM_CHECK_LAUNCH();
-    return CHAM_OK;
-}
-
-template <int BM, int BN, int WM, int WN, int BK, bool AK, bool BKC, int NP>
+// one tile instance: tile counts, epilogue and row-scale rules in gemm_tile.h's ladder (the same as gemm.hip's)
+template <int BM, int BN, int WM, int WN, bool AK, bool BKC, int NP>
 static int x3_launch_cfg(GemmParams& p, hipStream_t st) {
-    p.nbm = (p.M + BM - 1) / BM;
-    p.nbn = (p.N + BN - 1) / BN;
-    // epilogues per layout as in gemm.hip's launch_cfg: NN plain | bias (+ leaky | tanh); NT plain | x act'(dref); TN plain | split-K partial
-    constexpr bool NN = AK && !BKC, NT = AK && BKC, TN = !AK && !BKC;
-    if (p.splits > 1) {
-        if constexpr (TN) {
-            p.xcd_split = (p.splits % 8 == 0) ? 1 : 0;
-            const int rc = x3_launch_epi<BM, BN, WM, WN, BK, AK, BKC, 6, NP>(p, st);
-            if (rc != CHAM_OK) return rc;
-            launch_splitk_reduce(p, st);
-            CHAM_CHECK_LAUNCH();
-            return CHAM_OK;
-        } else {
-            return -CHAM_ERR_ARG;
-        }
-    }
-    if (p.dref) {
-        if (p.bias || p.act != ACT_NONE) return -CHAM_ERR_ARG;
-        if constexpr (NT) {
-            if (p.dact == ACT_LEAKY) return x3_launch_epi<BM, BN, WM, WN, BK, AK, BKC, 3, NP>(p, st);
-            if (p.dact == ACT_TANH) return x3_launch_epi<BM, BN, WM, WN, BK, AK, BKC, 4, NP>(p, st);
-        }
-        return -CHAM_ERR_ARG;
-    }
-    if (p.bias || p.act != ACT_NONE) {
-        if (!p.bias || p.accumulate) return -CHAM_ERR_ARG;
-        if constexpr (NN) {
-            if (p.act == ACT_LEAKY) return x3_launch_epi<BM, BN, WM, WN, BK, AK, BKC, 1, NP>(p, st);
-            if (p.act == ACT_TANH) return x3_launch_epi<BM, BN, WM, WN, BK, AK, BKC, 2, NP>(p, st);
-            return x3_launch_epi<BM, BN, WM, WN, BK, AK, BKC, 5, NP>(p, st);
-        }
-        return -CHAM_ERR_ARG;
-    }
-    return x3_launch_epi<BM, BN, WM, WN, BK, AK, BKC, 0, NP>(p, st);
+    constexpr int NTH = WM * WN * 64;
+    constexpr size_t smem = (size_t)2 * NP * (StageX3<BM, 16, AK, NTH, false>::PLANE + StageX3<BN, 16, BKC, NTH, false>::PLANE) * 2;
+    return tile_ladder_f32<BM, BN, AK, BKC>(p, g_x3_launches + 6, st, [&](auto epi, auto rs) {
+        constexpr int EPI = decltype(epi)::value;
+        return tile_launch<gemm_x3_kernel<BM, BN, WM, WN, AK, BKC, EPI, decltype(rs)::value, NP>>(p, EPI, NTH, smem, g_x3_launches + 6, st);
+    });
 }
 
 static int g_x3_variant = -1;     // -1 = automatic; 0 = 128x128 / 4 waves, 2 = 256x128 / 8 waves
 extern "C" void cham_gemm_f32x3_set_variant(int v) { g_x3_variant = v; }
 
+// tile_plan's tile index -> instance; the tile counter ([4] / [5] for the two-plane form) moves before the ladder can reject the call
 template <bool AK, bool BKC, int NP>
 static int x3_by_shape(GemmParams& p, hipStream_t st) {
-    auto grid = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * p.splits; };
-    int v = ((long)p.M * p.N >= (1L << 20) && grid(256, 128) >= 256) ? 2 : 0;
-    if (g_x3_variant >= 0) v = g_x3_variant;
-    switch (v) {
-        case 2: ++g_x3_launches[NP == 2 ? 5 : 1]; return x3_launch_cfg<256, 128, 4, 2, 16, AK, BKC, NP>(p, st);
-        default: ++g_x3_launches[NP == 2 ? 4 : 0]; return x3_launch_cfg<128, 128, 2, 2, 16, AK, BKC, NP>(p, st);
-    }
+    const int t = tile_plan::tile_x3(p.M, p.N, p.splits, g_x3_variant);
+    ++g_x3_launches[(NP == 2 ? 4 : 0) + t];
+    if (t == 1) return x3_launch_cfg<256, 128, 4, 2, AK, BKC, NP>(p, st);
+    return x3_launch_cfg<128, 128, 2, 2, AK, BKC, NP>(p, st);
 }
-
-extern "C" int cham_gemm_f32(const float* A, int lda, int transA, const float* B, int ldb, int transB, float* C, int ldc, int M, int N, int K,
-                             const float* bias, int act, const float* dref, int ldr, int dact, const float* rowscale, int ldrs, int rs_div,
-                             int accumulate, float* workspace, size_t workspace_bytes, int splits_hint, void* stream);
 
 extern "C" int cham_gemm_f32x3(const float* A, int lda, int transA, const float* B, int ldb, int transB,
                                float* C, int ldc, int M, int N, int K,
