@@ -148,6 +148,8 @@ _SIGNATURES = {
     "cham_acr_conv_pool_fwd": (c_int, [P, c_int, c_int, P, c_int64, c_int, c_int64, P, c_int, c_int, P, P, P, c_int, P, P, c_size_t, P]),
     "cham_acr_conv_pool_bwd": (c_int, [P, c_int, c_int, P, c_int64, c_int, c_int64, P, c_int, c_int, P, P, c_int, P, P, P, P]),
     "cham_acr_softmax_xent": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+    "cham_acr_sigmoid_xent_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cham_acr_sigmoid_xent": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, c_int, P, P, c_size_t, P]),
     "cham_acr_relu": (c_int, [P, c_size_t, P]),
     "cham_acr_act_bwd": (c_int, [P, P, c_size_t, c_int, P]),
 }

@@ -4,12 +4,23 @@
     conv_k[b,t,f] = relu(bias_k[f] + sum_{j<k} sum_e x[b,t+j,e] W_k[j,e,f]),  t = 0..L-k      one per size in cnn_filter_sizes
     pool         = concat_k max_t conv_k                    [B, n_sizes F]
     fc2          = relu(pool W_a + b_a);  ace = tanh(fc2 W_h + b_h)   -> the exported Article Content Embedding
-    logits_l     = ace W_l + b_l                            one multiclass head per label feature
+    logits_l     = ace W_l + b_l                            one head per label feature, multiclass or multilabel
     loss         = sum_l CE_l + l2_reg_lambda sum_kernels sum(w^2) / 2
 
-Built: text_feature_extractor = CNN, training_task = metadata_classification, multiclass heads, optional per-class weights.  Refused
-(NotImplementedError / ValueError naming the flag): the cuDNN LSTM / GRU extractors, the autoencoder task, multilabel heads,
+A multiclass head's CE is the sparse softmax cross-entropy with optional per-class weights.  A multilabel head's (ACR_ModelMultilabel
+only, see below) is the sigmoid cross-entropy against a multi-hot target built from the batch's zero-padded id lists [B, Kmax]:
+    z[b,c] = #{k : ids[b,k] == c} for c >= 1 (a duplicated id counts twice), z[b,0] = 0 (the padding id)
+    CE     = mean_b mean_c (max(x,0) - x z + log1p(exp(-|x|)));   prediction = x > 0 (uint8 multi-hot);   no class weights
+(acr_model.py:202-215, :6-8).  The multi-hot matrix is built inside the kernel and never reaches memory (csrc/acr.hip).
+
+Built: text_feature_extractor = CNN, training_task = metadata_classification, multiclass heads with optional per-class weights,
+multilabel heads.  Refused (NotImplementedError / ValueError naming the flag): the cuDNN LSTM / GRU extractors, the autoencoder task,
 dropout_keep_prob < 1.
+
+Multilabel heads are OPT-IN: ACR_Model and check_supported refuse them as they did before the head was built, ACR_ModelMultilabel (what
+acr_trainer_adressa constructs) and check_supported(..., multilabel=True) accept them.  The G1 trainer's contract - a multilabel head in
+its label features is an error that names the head - is part of its tested interface, and a model without such a head launches exactly
+the kernels it launched before.
 
 All parameters live in ONE flat fp32 buffer, the L2-regularised kernels first (``n_reg``), then the biases.  Widths that cham_gemm_f32
 needs as multiples of 4 (n_sizes F, acr_embeddings_size, every cardinality) are padded with zero rows / columns; zero-initialised
@@ -49,16 +60,18 @@ def check_flags(training_task, text_feature_extractor, dropout_keep_prob=1.0):
         raise NotImplementedError("--dropout_keep_prob < 1 is not built (the shipped launch scripts use 1.0)")
 
 
-def check_supported(training_task, text_feature_extractor, labels_features_config, params):
-    """check_flags plus the label heads: only multiclass heads with a cardinality are built."""
+def check_supported(training_task, text_feature_extractor, labels_features_config, params, multilabel=False):
+    """check_flags plus the label heads: multiclass heads with a cardinality, and multilabel heads when ``multilabel`` is set.
+    The opt-in keeps the G1 path's refusal (see the module docstring); ACR_ModelMultilabel passes True."""
     check_flags(training_task, text_feature_extractor, params.get('dropout_keep_prob', 1.0))
     if not labels_features_config:
         raise ValueError("label_features is empty: metadata_classification needs at least one label head")
     for name, cfg in labels_features_config.items():
         ct = cfg.get('classification_type')
-        if ct == 'multilabel':
-            raise NotImplementedError("label feature %r: classification_type multilabel is not built; only multiclass" % name)
-        if ct != 'multiclass':
+        if ct == 'multilabel' and not multilabel:
+            raise NotImplementedError("label feature %r: classification_type multilabel is not accepted here, only multiclass "
+                                      "(multilabel heads are opt-in: ACR_ModelMultilabel, acr_trainer_adressa)" % name)
+        if ct not in ('multiclass', 'multilabel'):
             raise ValueError("label feature %r: classification_type %r invalid" % (name, ct))
         if int(cfg.get('cardinality', 0)) < 1:
             raise ValueError("label feature %r needs a cardinality" % name)
@@ -140,8 +153,9 @@ class ACRLayout:
         return m
 
 
-def validate_batch(text, labels, vocab_size, heads):
-    """Host-side range checks BEFORE any upload: an out-of-range id becomes a ValueError, never a GPU fault."""
+def validate_batch(text, labels, vocab_size, heads, multilabel_heads=()):
+    """Host-side range checks BEFORE any upload: an out-of-range id becomes a ValueError, never a GPU fault.  The labels of a head named
+    in ``multilabel_heads`` are a zero-padded id list [B, Kmax] (Kmax = 0 is legal), those of any other head one id per row."""
     text = np.asarray(text)
     if text.ndim != 2 or text.shape[0] < 1:
         raise ValueError("text must be [B, L], got shape %r" % (text.shape,))
@@ -149,18 +163,26 @@ def validate_batch(text, labels, vocab_size, heads):
         raise ValueError("text holds a token id outside [0, %d): min %d, max %d" % (vocab_size, text.min(), text.max()))
     if labels is not None:
         for n, c in heads.items():
-            y = np.asarray(labels[n]).reshape(-1)
+            y = np.asarray(labels[n])
+            if n in multilabel_heads:
+                if y.ndim != 2:
+                    raise ValueError("label %r (multilabel) must be [B, Kmax], got shape %r" % (n, y.shape))
+            else:
+                y = y.reshape(-1)
             if y.shape[0] != text.shape[0]:
                 raise ValueError("label %r has %d rows, text has %d" % (n, y.shape[0], text.shape[0]))
-            if y.min() < 0 or y.max() >= c:
+            if y.size and (y.min() < 0 or y.max() >= c):
                 raise ValueError("label %r holds an id outside [0, %d): min %d, max %d" % (n, c, y.min(), y.max()))
 
 
 class ACR_Model:
-    """train_step / eval_step / predict over numpy batches (features['text'] [B, L], labels {head: [B]})."""
+    """train_step / eval_step / predict over numpy batches (features['text'] [B, L], labels {head: [B]}; a multilabel head's labels
+    are the zero-padded id lists [B, Kmax], accepted by ACR_ModelMultilabel only)."""
+
+    MULTILABEL_HEADS = False          # the opt-in (module docstring): ACR_ModelMultilabel sets it
 
     def __init__(self, training_task, text_feature_extractor, labels_features_config, params, device=None, seed=RANDOM_SEED):
-        check_supported(training_task, text_feature_extractor, labels_features_config, params)
+        check_supported(training_task, text_feature_extractor, labels_features_config, params, multilabel=self.MULTILABEL_HEADS)
         import torch
         from .. import _lib
         self.torch, self._lib_mod = torch, _lib
@@ -176,6 +198,7 @@ class ACR_Model:
         # feature_weight_on_loss: the reference reads it from the dict of ALL label features instead of the feature's own entry
         # (acr_model.py:219), so it is always 1.0; kept - every head's loss enters with weight 1.
         heads = OrderedDict((n, cfg['cardinality']) for n, cfg in labels_features_config.items())
+        self.multilabel = tuple(n for n, cfg in labels_features_config.items() if cfg['classification_type'] == 'multilabel')
         self.layout = L = ACRLayout(E, sizes, params['cnn_num_filters'], params['acr_embeddings_size'], heads)
         t = torch.zeros((self.V, self.ldE), dtype=torch.float32)
         t[:, :E] = torch.from_numpy(table)
@@ -187,7 +210,7 @@ class ACR_Model:
         self.global_step = 0
         self.class_weights = {}
         for n, w in (params.get('labels_class_weights') or {}).items():
-            if n in heads:
+            if n in heads and n not in self.multilabel:                   # (the multilabel loss takes no class weights, :214)
                 w = np.asarray(w, np.float32).reshape(-1)
                 if w.shape[0] != heads[n]:
                     raise ValueError("labels_class_weights[%r] has %d entries, cardinality is %d" % (n, w.shape[0], heads[n]))
@@ -225,7 +248,12 @@ class ACR_Model:
                      ace=z(B, L.ldA), dace=z(B, L.ldA), row_ws=z(B),
                      colsum_ws=z(max(1, self.lib.cham_colsum_workspace_bytes(B, max([L.ldA] + list(L.ldC.values()))) // 4)))
             for n in L.heads:
-                d['logits_' + n] = z(B, L.ldC[n]); d['dlogits_' + n] = z(B, L.ldC[n]); d['pred_' + n] = z(B, dt=self.torch.int32)
+                d['logits_' + n] = z(B, L.ldC[n]); d['dlogits_' + n] = z(B, L.ldC[n])
+                if n not in self.multilabel:
+                    d['pred_' + n] = z(B, dt=self.torch.int32)
+            for n in self.multilabel:                                   # uint8 multi-hot predictions, (tp, fp, fn), the partials
+                d['pred_' + n] = z(B, L.ldC[n], dt=self.torch.uint8); d['counts_' + n] = z(3, dt=self.torch.int32)
+                d['ml_ws_' + n] = z(max(1, self.lib.cham_acr_sigmoid_xent_workspace_bytes(B, L.heads[n]) // 4))
             self._bufs[B] = d
         return self._bufs[B]
 
@@ -235,7 +263,7 @@ class ACR_Model:
 
     def _upload(self, features, labels):
         text = np.asarray(features['text'])
-        validate_batch(text, labels, self.V, self.layout.heads)
+        validate_batch(text, labels, self.V, self.layout.heads, self.multilabel)
         kmax = max(self.layout.sizes)
         if text.shape[1] < kmax:
             raise ValueError("the batch's padded length %d is below the largest cnn_filter_sizes entry %d (the reference yields an "
@@ -244,7 +272,10 @@ class ACR_Model:
         lab = None
         if labels is not None:
             lab = {n: self.torch.from_numpy(np.ascontiguousarray(np.asarray(labels[n]).reshape(-1), dtype=np.int32)).to(self.device)
-                   for n in self.layout.heads}
+                   for n in self.layout.heads if n not in self.multilabel}
+            for n in self.multilabel:                                     # [B, Kmax] int32; Kmax = 0 -> no list at all (a NULL pointer)
+                ids = np.ascontiguousarray(labels[n], dtype=np.int32)
+                lab[n] = self.torch.from_numpy(ids).to(self.device) if ids.shape[1] else None
         return tok, lab
 
     # ---- forward / backward
@@ -272,6 +303,9 @@ class ACR_Model:
     def _losses(self, buf, lab, B, with_grad):
         L, lib, st, ptr = self.layout, self.lib, self._stream(), self._lib_mod.ptr
         for i, n in enumerate(L.heads):
+            if n in self.multilabel:
+                self._sigmoid_xent(buf, n, B, lab[n], self.loss_terms.data_ptr() + 4 * i, with_grad)
+                continue
             self._check(lib.cham_acr_softmax_xent(ptr(buf['logits_' + n]), L.ldC[n], B, L.heads[n], None if lab is None else ptr(lab[n]),
                                                   ptr(self.class_weights.get(n)), self.loss_terms.data_ptr() + 4 * i,
                                                   ptr(buf['dlogits_' + n]) if with_grad else None, ptr(buf['pred_' + n]), ptr(buf['row_ws']),
@@ -279,6 +313,16 @@ class ACR_Model:
         self._check(lib.cham_sumsq_partial(ptr(self.params), L.n_reg, ptr(self.sumsq), st), "cham_sumsq_partial")
         self._check(lib.cham_loss_finalize(ptr(self.loss_terms), len(L.heads), 1.0, ptr(self.sumsq), self.l2_reg_lambda, ptr(self.loss), st),
                     "cham_loss_finalize")
+
+    def _sigmoid_xent(self, buf, n, B, ids, loss_slot, with_grad):
+        """The multilabel head ``n``: ids = the device id lists [B, Kmax] or None (no list: every target is 0)."""
+        L, ptr = self.layout, self._lib_mod.ptr
+        K = 0 if ids is None else ids.shape[1]
+        ws = buf['ml_ws_' + n]
+        self._check(self.lib.cham_acr_sigmoid_xent(ptr(buf['logits_' + n]), L.ldC[n], B, L.heads[n], ptr(ids), K, K, loss_slot,
+                                                   ptr(buf['dlogits_' + n]) if with_grad else None, ptr(buf['pred_' + n]), L.ldC[n],
+                                                   ptr(buf['counts_' + n]), ptr(ws), ws.numel() * 4, self._stream()),
+                    "cham_acr_sigmoid_xent")
 
     def _backward(self, tok, buf):
         L, lib, st, ptr = self.layout, self.lib, self._stream(), self._lib_mod.ptr
@@ -325,7 +369,8 @@ class ACR_Model:
         return self.loss
 
     def eval_step(self, features, labels):
-        """Loss and predictions of a batch without an update: (loss [3] numpy, {head: predictions [B]})."""
+        """Loss and predictions of a batch without an update: (loss [3] numpy, predictions()); the (tp, fp, fn) of the multilabel
+        heads are then in multilabel_counts()."""
         tok, lab = self._upload(features, labels)
         buf = self._forward(tok)
         self._losses(buf, lab, tok.shape[0], False)
@@ -333,12 +378,15 @@ class ACR_Model:
         return self.loss.cpu().numpy(), self.predictions()
 
     def predict(self, features):
-        """(acr_embedding [B, acr_embeddings_size] float32, {head: predictions [B]}) of a batch at ITS padded length."""
+        """(acr_embedding [B, acr_embeddings_size] float32, predictions()) of a batch at ITS padded length."""
         tok, _ = self._upload(features, None)
         buf = self._forward(tok)
         lib, ptr, L = self.lib, self._lib_mod.ptr, self.layout
         dummy = self.torch.zeros(tok.shape[0], dtype=self.torch.int32, device=self.device)
         for n in L.heads:          # only the argmax output is used: PREDICT has no labels (all-zero labels, the loss slot is scratch)
+            if n in self.multilabel:
+                self._sigmoid_xent(buf, n, tok.shape[0], None, self.loss_terms.data_ptr(), False)
+                continue
             self._check(lib.cham_acr_softmax_xent(ptr(buf['logits_' + n]), L.ldC[n], tok.shape[0], L.heads[n], ptr(dummy), None,
                                                   self.loss_terms.data_ptr(), None, ptr(buf['pred_' + n]), ptr(buf['row_ws']), self._stream()),
                         "cham_acr_softmax_xent")
@@ -346,7 +394,15 @@ class ACR_Model:
         return buf['ace'][:, :L.A].cpu().numpy(), self.predictions()
 
     def predictions(self):
-        return {n: self._last['pred_' + n].cpu().numpy().astype(np.int64) for n in self.layout.heads}
+        """{head: argmax [B] int64 (multiclass) or the multi-hot x > 0 [B, C] uint8 (multilabel)} of the last batch."""
+        L = self.layout
+        return {n: self._last['pred_' + n][:, :L.heads[n]].cpu().numpy() if n in self.multilabel
+                else self._last['pred_' + n].cpu().numpy().astype(np.int64) for n in L.heads}
+
+    def multilabel_counts(self):
+        """{multilabel head: (tp, fp, fn)} of the last batch, counted on the device against the batch's multi-hot targets (after predict,
+        which has no labels: tp = fn = 0)."""
+        return {n: tuple(int(v) for v in self._last['counts_' + n].cpu().numpy()) for n in self.multilabel}
 
     # ---- host views (tests, checkpoints)
     def logical_weights(self):
@@ -365,3 +421,10 @@ class ACR_Model:
             raise ValueError("checkpoint holds %d parameters, the model has %d" % (sd['params'].numel(), self.params.numel()))
         self.params.copy_(sd['params']); self.m.copy_(sd['m']); self.v.copy_(sd['v'])
         self.global_step = int(sd['global_step'])
+
+
+class ACR_ModelMultilabel(ACR_Model):
+    """ACR_Model that also accepts multilabel heads (the Adressa label set: category0 multiclass + keywords multilabel).  A class of
+    its own because the base class's refusal of such a head is part of the G1 trainer's tested interface (module docstring)."""
+
+    MULTILABEL_HEADS = True

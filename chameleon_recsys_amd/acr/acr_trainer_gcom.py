@@ -126,11 +126,13 @@ PREDICT_METADATA = ('article_id', 'category_id', 'publisher_id', 'created_at_ts'
 
 
 def _variables(params):
-    """The model of params['variable_store'], created on first use (the graph's variables of the reference)."""
+    """The model of params['variable_store'], created on first use (the graph's variables of the reference).  params['model_class']
+    (default ACR_Model) is the class to construct: acr_trainer_adressa passes ACR_ModelMultilabel."""
     store = params.setdefault('variable_store', {})
     if store.get('model') is None:
-        store['model'] = ACR_Model(params['training_task'], params['text_feature_extractor'], params['features_config']['label_features'],
-                                   params, device=params.get('device'), seed=params.get('tf_random_seed', RANDOM_SEED))
+        cls = params.get('model_class', ACR_Model)
+        store['model'] = cls(params['training_task'], params['text_feature_extractor'], params['features_config']['label_features'],
+                             params, device=params.get('device'), seed=params.get('tf_random_seed', RANDOM_SEED))
     return store['model']
 
 

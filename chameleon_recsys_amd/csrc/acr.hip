@@ -301,6 +301,132 @@ extern "C" int cham_acr_softmax_xent(const float* logits, int ld, int B, int C, 
     return CHAM_OK;
 }
 
+// ---- sigmoid cross-entropy of one MULTILABEL head (acr_model.py:202-215; predictions :6-8; precision / recall :254-268) against the
+// multi-hot target built from a ragged, zero-padded id list, which never reaches memory:
+//   z[b,c] = #{k < K : ids[b,k] == c} for c >= 1 (reduce_sum(one_hot): a duplicated id counts twice), z[b,0] = 0 (the padding id);
+//   term = max(x,0) - x z + log1p(exp(-|x|));  loss = sum term / (B C);  dlogits = (sigmoid(x) - z) / (B C), 0 in the padded columns;
+//   pred = x > 0;  counts = (tp, fp, fn) over c < C.
+// Grid (column chunks of ACR_ML_CHUNK, rows).  A workgroup counts the row's ids that fall into its chunk into LDS (integer adds; an id
+// outside [1, C) is ignored, one_hot's rule, so no id can index outside the chunk), then each lane takes 4 consecutive columns.  Float
+// sums: the lane's 4 terms ascending, the butterfly wave sum, the 4 waves ascending -> one partial per (row, chunk); a single final
+// workgroup adds the partials in a fixed order.  Counts are integers.  No float atomics: two runs are bit-identical.
+#define ACR_ML_CHUNK 1024    /* columns per workgroup = 256 lanes x 4; one int of LDS per column */
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// the three per-workgroup counts: wave sums, then integer LDS adds; valid in cred[] after the trailing barrier
+__device__ __forceinline__ void acr_block_counts(int tp, int fp, int fn, int* cred) {
+    tp = wave_sum_int(tp); fp = wave_sum_int(fp); fn = wave_sum_int(fn);
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&cred[0], tp); atomicAdd(&cred[1], fp); atomicAdd(&cred[2], fn); }
+    __syncthreads();
+}
+__global__ __launch_bounds__(256) void k_acr_sigmoid_xent(const float* __restrict__ logits, int ld, int C, const int32_t* __restrict__ ids,
+                                                          int K, int ldK, float inv_n, float* __restrict__ dlogits,
+                                                          uint8_t* __restrict__ pred, int ldp, float* __restrict__ part,
+                                                          int32_t* __restrict__ cpart, int vec) {
+    __shared__ __attribute__((aligned(16))) int zc[ACR_ML_CHUNK];
+    __shared__ float red[4];
+    __shared__ int cred[3];
+    const int b = blockIdx.y, c0 = blockIdx.x * ACR_ML_CHUNK, cl = 4 * threadIdx.x, c = c0 + cl;
+    const int hi = min(C, c0 + ACR_ML_CHUNK), lo = max(c0, 1);
+    *reinterpret_cast<int4*>(zc + cl) = make_int4(0, 0, 0, 0);
+    if (threadIdx.x < 3) cred[threadIdx.x] = 0;
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const int id = ids[(size_t)b * ldK + k];
+        if (id >= lo && id < hi) atomicAdd(&zc[id - c0], 1);
+    }
+    __syncthreads();
+    const float* xr = logits + (size_t)b * ld;
+    const int n = min(4, C - c);                             // this lane's columns inside [0, C); <= 0 for the lanes beyond
+    float x[4] = {0.f, 0.f, 0.f, 0.f}, d[4];
+    if (n == 4 && vec) {
+        const float4 v = ld4(xr + c);
+        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    } else {
+        for (int u = 0; u < n; ++u) x[u] = xr[c + u];        // (the padded columns [C, ld) are never read)
+    }
+    const int4 z4 = *reinterpret_cast<const int4*>(zc + cl);
+    const int z[4] = {z4.x, z4.y, z4.z, z4.w};
+    float s = 0.f;
+    int tp = 0, fp = 0, fn = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const float zf = (float)z[u], e = expf(-fabsf(x[u]));
+        const float term = (fmaxf(x[u], 0.f) - x[u] * zf) + log1pf(e);
+        const float sig = (x[u] >= 0.f ? 1.f : e) / (1.f + e);
+        const bool p = x[u] > 0.f, in = u < n;
+        d[u] = in ? (sig - zf) * inv_n : 0.f;
+        if (in) {
+            s += term;
+            tp += p && z[u] > 0; fp += p && z[u] == 0; fn += !p && z[u] > 0;
+            pred[(size_t)b * ldp + c + u] = p ? 1 : 0;
+        }
+    }
+    if (dlogits) {
+        float* dr = dlogits + (size_t)b * ld;
+        if (vec && c + 3 < min(ld, c0 + ACR_ML_CHUNK)) {
+            if (n > 0) st4(dr + c, make_float4(d[0], d[1], d[2], d[3]));     // (a group that straddles C writes the zeros of [C, c + 4) too)
+        } else {
+            for (int u = 0; u < n; ++u) dr[c + u] = d[u];
+        }
+        if (blockIdx.x == gridDim.x - 1)                     // the last chunk zero-fills [C, ld) (what a straddling float4 wrote is 0 already)
+            for (int cc = C + threadIdx.x; cc < ld; cc += 256) dr[cc] = 0.f;
+    }
+    s = block_sum(s, red);
+    acr_block_counts(tp, fp, fn, cred);
+    const size_t o = (size_t)b * gridDim.x + blockIdx.x;
+    if (threadIdx.x == 0) part[o] = s;
+    if (threadIdx.x < 3) cpart[3 * o + threadIdx.x] = cred[threadIdx.x];
+}
+__global__ __launch_bounds__(256) void k_acr_sigmoid_xent_loss(const float* __restrict__ part, const int32_t* __restrict__ cpart, int n_part,
+                                                               float inv_n, float* __restrict__ loss, int32_t* __restrict__ counts) {
+    __shared__ float red[4];
+    __shared__ int cred[3];
+    if (threadIdx.x < 3) cred[threadIdx.x] = 0;
+    float s = 0.f;
+    int tp = 0, fp = 0, fn = 0;
+    for (int i = threadIdx.x; i < n_part; i += 256) {
+        s += part[i];
+        tp += cpart[3 * i]; fp += cpart[3 * i + 1]; fn += cpart[3 * i + 2];
+    }
+    s = block_sum(s, red);                                   // (its barriers also order the zeroing of cred before the adds below)
+    acr_block_counts(tp, fp, fn, cred);
+    if (threadIdx.x == 0) loss[0] = s * inv_n;
+    if (threadIdx.x < 3) counts[threadIdx.x] = cred[threadIdx.x];
+}
+
+static long long acr_ml_chunks(int C) { return ((long long)C + ACR_ML_CHUNK - 1) / ACR_ML_CHUNK; }
+
+extern "C" size_t cham_acr_sigmoid_xent_workspace_bytes(int B, int C) {
+    if (B <= 0 || C <= 0) return 0;
+    return (size_t)B * (size_t)acr_ml_chunks(C) * (sizeof(float) + 3 * sizeof(int32_t));
+}
+
+extern "C" int cham_acr_sigmoid_xent(const float* logits, int ld, int B, int C, const int32_t* label_ids, int K, int ldK, float* loss,
+                                     float* dlogits, uint8_t* pred, int ldp, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    if (!logits || !loss || !pred || !counts || !workspace || B <= 0 || B > 65535 || C <= 0 || ld < C || ldp < C) return -CHAM_ERR_ARG;
+    if (K < 0 || ldK < K || (K > 0 && !label_ids)) return -CHAM_ERR_ARG;
+    const long long n_part = (long long)B * acr_ml_chunks(C);
+    if ((long long)B * C > 0x7fffffffLL || n_part > 0x7fffffffLL) return -CHAM_ERR_ARG;                // (the counts are int32)
+    if (workspace_bytes < cham_acr_sigmoid_xent_workspace_bytes(B, C) || ((uintptr_t)workspace & 3)) return -CHAM_ERR_ARG;
+    const int vec = !(ld & 3) && !((uintptr_t)logits & 15) && !((uintptr_t)dlogits & 15);
+    const float inv_n = (float)(1.0 / ((double)B * (double)C));
+    float* part = reinterpret_cast<float*>(workspace);
+    int32_t* cpart = reinterpret_cast<int32_t*>(part + n_part);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_acr_sigmoid_xent, dim3((unsigned)acr_ml_chunks(C), B), dim3(256), 0, st, logits, ld, C, label_ids, K, ldK, inv_n, dlogits,
+                       pred, ldp, part, cpart, vec);
+    CHAM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_acr_sigmoid_xent_loss, dim3(1), dim3(256), 0, st, part, cpart, (int)n_part, inv_n, loss, counts);
+    CHAM_CHECK_LAUNCH();
+    return CHAM_OK;
+}
+
 // ---- the dense layers' small elementwise pieces (cham_gemm_f32 has no ReLU epilogue).  act: 0 = ReLU, 1 = tanh; y = the saved
 // POST-activation value.  In place; n % 4 == 0 (padded widths).
 __global__ __launch_bounds__(256) void k_acr_relu(float* __restrict__ x, size_t n4) {

@@ -639,6 +639,19 @@ int cham_acr_conv_pool_bwd(const int32_t* tokens, int B, int L, const float* tab
  * with the first index on ties; row_workspace [B] floats. */
 int cham_acr_softmax_xent(const float* logits, int ld, int B, int C, const int32_t* labels, const float* class_weights, float* loss,
                           float* dlogits, int32_t* pred, float* row_workspace, void* stream);
+/* one MULTILABEL label head (reference acr_model.py:202-215, :6-8, :254-268): logits [B, ld] of true width C (columns [C, ld) are never
+ * read); label_ids int32 [B, K] with row stride ldK, zero-padded (K = 0 with a NULL pointer: every target is 0).  The multi-hot target
+ *   z[b,c] = #{k < K : label_ids[b,k] == c} for c >= 1 (a duplicated id counts twice), z[b,0] = 0 (the padding id)
+ * is built in LDS per (row, chunk of 1024 columns) and never reaches memory; an id outside [0, C) is ignored (one_hot's rule).
+ *   loss[0] = sum_{b, c<C} (max(x,0) - x z + log1p(exp(-|x|))) / (B C)         (no class weights)
+ *   dlogits [B, ld] (or NULL) = (sigmoid(x) - z) / (B C) for c < C, 0 for the padded columns
+ *   pred uint8 [B, ldp] (ldp >= C; only columns < C are written) = x > 0
+ *   counts int32 [3] = (tp, fp, fn) over c < C: tp = pred & z > 0, fp = pred & z == 0, fn = !pred & z > 0
+ * workspace: cham_acr_sigmoid_xent_workspace_bytes(B, C) bytes, 4-byte aligned.  Float sums have a fixed order and there are no float
+ * atomics: two runs are bit-identical.  B <= 65535, B C < 2^31; any argument outside the above: -EINVAL, nothing launched. */
+size_t cham_acr_sigmoid_xent_workspace_bytes(int B, int C);
+int cham_acr_sigmoid_xent(const float* logits, int ld, int B, int C, const int32_t* label_ids, int K, int ldK, float* loss, float* dlogits,
+                          uint8_t* pred, int ldp, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 /* x = relu(x) in place; dy *= act'(y) in place from the saved POST-activation y (act 0 = ReLU, 1 = tanh).  n % 4 == 0, 16-byte aligned. */
 int cham_acr_relu(float* x, size_t n, void* stream);
 int cham_acr_act_bwd(float* dy, const float* y, size_t n, int act, void* stream);

@@ -2,7 +2,7 @@
 """Cost of the ACR module (csrc/acr.hip, chameleon_recsys_amd/acr) at the G1 shape: B 64 articles x L 300 tokens, E 300, filter sizes
 3/4/5, F 128, vocabulary 45 000, acr_embeddings_size 250, one head of 461 classes.
 
-  python scripts/bench_acr.py [--iters 30] [--rounds 3] [--articles 1024] [--out DIR]
+  python scripts/bench_acr.py [--iters 30] [--rounds 3] [--articles 1024] [--legs conv,step,multilabel,pipeline] [--out DIR]
 
 One JSON line per leg, device events around each call, every shape warmed up first:
   conv_fwd   cham_acr_conv_pool_fwd (both launches) beside torch conv1d + relu + amax in fp32 on the same inputs - what a user would
@@ -10,6 +10,8 @@ One JSON line per leg, device events around each call, every shape warmed up fir
              fp32-matrix peak; the two results are compared at the timed size
   conv_bwd   cham_acr_conv_pool_bwd
   step       ACR_Model.train_step (upload, forward, loss, backward, Adam) on resident numpy batches
+  multilabel cham_acr_sigmoid_xent alone (B 64, K 20, C 1 000 and 6 500) and the Adressa-shaped train_step (L 300, E 300, sizes 3/4/5,
+             F 128, embedding 250, category0 of 41 classes) with and without the keywords head of 6 500 classes
   pipeline   articles/s through prepare_dataset -> train_step on a synthetic corpus of --articles articles of ~300 tokens, and of
              prepare_dataset alone (the record decoder is host-side Python)"""
 import argparse
@@ -125,6 +127,55 @@ def bench_step(s, dev, iters):
     return [out]
 
 
+ADRESSA = dict(B=64, L=300, E=300, F=128, sizes=(3, 4, 5), V=45000, A=250, C0=41, CK=6500, K=20)
+
+
+def bench_multilabel(lib, s, dev, iters):
+    """The multilabel head: cham_acr_sigmoid_xent alone at B 64, K 20 and C in {1 000, 6 500} (with dlogits), and the Adressa-shaped
+    train_step (category0 of 41 classes) with and without the keywords head of 6 500 classes."""
+    from chameleon_recsys_amd.acr.acr_model import ACR_ModelMultilabel
+    B, K = s['B'], s['K']
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    st = torch.cuda.current_stream().cuda_stream
+    lines = []
+    for C in (1000, s['CK']):
+        ld = (C + 3) // 4 * 4
+        logits = 3.0 * torch.randn(B, ld, generator=g, device=dev)
+        ids = torch.randint(1, C, (B, K), generator=g, device=dev, dtype=torch.int32)
+        loss, dl = torch.zeros(1, device=dev), torch.zeros(B, ld, device=dev)
+        pred, counts = torch.zeros(B, ld, dtype=torch.uint8, device=dev), torch.zeros(3, dtype=torch.int32, device=dev)
+        ws = torch.zeros(lib.cham_acr_sigmoid_xent_workspace_bytes(B, C) // 4, device=dev)
+
+        def head():
+            check(lib.cham_acr_sigmoid_xent(ptr(logits), ld, B, C, ptr(ids), K, K, ptr(loss), ptr(dl), ptr(pred), ld, ptr(counts), ptr(ws),
+                                            ws.numel() * 4, st), "cham_acr_sigmoid_xent")
+        med, mn = timed(head, iters)
+        lines.append(dict(leg='sigmoid_xent', B=B, K=K, C=C, ms_median=med, ms_min=mn, bytes_moved=B * ld * 9, loss=float(loss.cpu()[0])))
+        print(json.dumps(lines[-1]), flush=True)
+    rng = np.random.RandomState(0)
+    table = (0.5 * rng.randn(s['V'], s['E'])).astype(np.float32)
+    params = dict(word_embeddings_matrix=table, cnn_filter_sizes=','.join(map(str, s['sizes'])), cnn_num_filters=s['F'],
+                  acr_embeddings_size=s['A'], dropout_keep_prob=1.0, l2_reg_lambda=1e-3, learning_rate=1e-3)
+    for with_keywords in (False, True):
+        heads = {'category0': {'classification_type': 'multiclass', 'cardinality': s['C0']}}
+        if with_keywords:
+            heads['keywords'] = {'classification_type': 'multilabel', 'cardinality': s['CK']}
+        model = ACR_ModelMultilabel('metadata_classification', 'CNN', heads, params, device=dev)
+        batches = [({'text': rng.randint(0, s['V'], size=(B, s['L']))},
+                    {'category0': rng.randint(0, s['C0'], size=B), 'keywords': rng.randint(1, s['CK'], size=(B, K))}) for _ in range(4)]
+        i = [0]
+
+        def step():
+            f, l = batches[i[0] % 4]; i[0] += 1
+            model.train_step(f, l)
+        med, mn = timed(step, iters)
+        lines.append(dict(leg='step_adressa', keywords_head=with_keywords, ms_median=med, ms_min=mn, articles_per_s=B / (med * 1e-3),
+                          last_loss=float(model.loss.cpu()[0])))
+        print(json.dumps(lines[-1]), flush=True)
+    return lines
+
+
 def bench_pipeline(s, dev, n_articles):
     from chameleon_recsys_amd.acr import acr_datasets, acr_trainer_gcom, synthetic
     with tempfile.TemporaryDirectory() as d:
@@ -152,13 +203,20 @@ def main():
     ap.add_argument('--iters', type=int, default=30)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--articles', type=int, default=1024, help='0: no pipeline leg')
+    ap.add_argument('--legs', default='conv,step,multilabel,pipeline', help='comma-separated subset of conv,step,multilabel,pipeline')
     ap.add_argument('--out', default=None, help='also append the JSON lines to DIR/bench_acr.jsonl')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_acr.py needs a ROCm device")
     lib, dev = _lib.load(), torch.device('cuda:0')
-    lines = bench_conv(lib, G1, dev, args.iters, args.rounds) + bench_step(G1, dev, args.iters)
-    if args.articles > 0:
+    legs, lines = args.legs.split(','), []
+    if 'conv' in legs:
+        lines += bench_conv(lib, G1, dev, args.iters, args.rounds)
+    if 'step' in legs:
+        lines += bench_step(G1, dev, args.iters)
+    if 'multilabel' in legs:
+        lines += bench_multilabel(lib, ADRESSA, dev, args.iters)
+    if 'pipeline' in legs and args.articles > 0:
         lines += bench_pipeline(G1, dev, args.articles)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
