@@ -144,6 +144,7 @@ _SIGNATURES = {
     "cham_eval_coverage_seed": (c_int, [P, c_int, c_int64, P, P, P]),
     "cham_eval_coverage_workspace_bytes": (c_size_t, [c_int64]),
     "cham_eval_coverage_count": (c_int, [P, P, c_int64, P, c_size_t, P, P]),
+    "cham_eval_rank_hist": (c_int, [P, P, c_int, c_int, c_int, P, c_int64, P, P, c_int, P]),
     "cham_acr_conv_pool_workspace_bytes": (c_size_t, [c_int, c_int, P, c_int, c_int]),
     "cham_acr_conv_pool_fwd": (c_int, [P, c_int, c_int, P, c_int64, c_int, c_int64, P, c_int, c_int, P, P, P, c_int, P, P, c_size_t, P]),
     "cham_acr_conv_pool_bwd": (c_int, [P, c_int, c_int, P, c_int64, c_int, c_int64, P, c_int, c_int, P, P, c_int, P, P, P, P]),

@@ -14,6 +14,13 @@
 //                           label and clicked item as clicked): every writer stores the byte 1.
 //   k_cov_seed              clicked map <- the recent-clicks buffer (a 0 included for empty slots, like set(buffer) in the reference).
 //   k_cov_partial/_final    byte counts of both maps: per-block partial sums into a workspace, then one block adds them (integers).
+//   k_eval_rank_hist        HitRate@n / MRR@n / NDCG@n / HitRate-by-position are functions of ONE integer histogram: how many valid clicks
+//                           at session position t had their positive ranked at r (cham_rank_items' label_rank; ranks >= topn share the
+//                           last bin).  One workgroup per position t; threads stride over the rows b and count into LDS integers
+//                           (integer LDS atomics: order-free).  The global record ACCUMULATES over launches: element (t, r) has exactly
+//                           one writer per launch (plain 64-bit read-add-write; launches are stream-ordered).  The fp64 sum of the labels'
+//                           normalised popularity has a fixed order - each thread's own strided terms ascending, then a fixed LDS tree -
+//                           so two runs are bit-identical.  No float atomics.
 #include "common.h"
 
 #define EVAL_MAX_TOPN 64
@@ -199,6 +206,51 @@ __global__ __launch_bounds__(256) void k_cov_final(const int64_t* __restrict__ p
         __syncthreads();
     }
     if (threadIdx.x < 2) counts[threadIdx.x] = red[threadIdx.x][0];
+}
+
+#define HIST_THREADS 256
+#define HIST_MAX_TOPN 256
+
+__global__ __launch_bounds__(HIST_THREADS) void k_eval_rank_hist(const int32_t* __restrict__ label_rank, const int64_t* __restrict__ labels,
+                                                                 int B, int T, int topn, const float* __restrict__ pop_norm,
+                                                                 int64_t n_items, int64_t* __restrict__ hist, double* __restrict__ pop_sum) {
+    __shared__ int s_hist[HIST_MAX_TOPN + 1];
+    __shared__ double s_sum[HIST_THREADS];
+    const int t = blockIdx.x;                        // < T (the grid), T <= t_cap (checked by the host entry)
+    const int tid = threadIdx.x;
+    for (int k = tid; k <= topn; k += HIST_THREADS) s_hist[k] = 0;
+    __syncthreads();
+    double acc = 0.0;
+    for (int b = tid; b < B; b += HIST_THREADS) {    // ascending b per thread
+        const int64_t at = (int64_t)b * T + t;
+        const int r = label_rank[at];
+        if (r < 0) continue;                         // padded position
+        atomicAdd(&s_hist[r < topn ? r : topn], 1);
+        if (pop_norm != nullptr) {
+            const int64_t id = labels[at];
+            if (id >= 0 && id < n_items) acc += (double)pop_norm[id];
+        }
+    }
+    s_sum[tid] = acc;
+    __syncthreads();
+    for (int s = HIST_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) s_sum[tid] += s_sum[tid + s];
+        __syncthreads();
+    }
+    int64_t* row = hist + (int64_t)t * (topn + 1);
+    for (int k = tid; k <= topn; k += HIST_THREADS) row[k] += (int64_t)s_hist[k];
+    if (tid == 0 && pop_norm != nullptr) pop_sum[t] += s_sum[0];
+}
+
+extern "C" int cham_eval_rank_hist(const int32_t* label_rank, const int64_t* labels, int B, int T, int topn, const float* pop_norm,
+                                   int64_t n_items, int64_t* hist, double* pop_sum, int t_cap, void* stream) {
+    if (!label_rank || !labels || !hist || !pop_sum || B < 1 || T < 1 || topn < 1 || topn > HIST_MAX_TOPN || T > t_cap ||
+        (pop_norm != nullptr && n_items < 1))
+        return -CHAM_ERR_ARG;
+    hipLaunchKernelGGL(k_eval_rank_hist, dim3((unsigned)T), dim3(HIST_THREADS), 0, (hipStream_t)stream, label_rank, labels, B, T, topn,
+                       pop_norm, n_items, hist, pop_sum);
+    CHAM_CHECK_LAUNCH();
+    return CHAM_OK;
 }
 
 extern "C" int cham_eval_beyond_accuracy(const int64_t* pred_ids, int NC, const int64_t* labels, const int64_t* clicked, int BT,

@@ -277,7 +277,8 @@ class Estimator:
                 torch.cuda.synchronize()
                 dt = time.time() - t0
                 self.steps_per_sec = n / dt
-                print("INFO:global_step/sec: %.4g (step %d)" % (n / dt, self.global_step), flush=True)
+                if getattr(self._store.get('runtime'), 'dp_rank', 0) == 0:      # (data parallel: the first rank speaks for all)
+                    print("INFO:global_step/sec: %.4g (step %d)" % (n / dt, self.global_step), flush=True)
                 last_log = n
             # (called every step whatever save_checkpoints_secs says: under data parallelism it is also the cross-rank poll of the
             # kernel time-out word, every CKPT_DECISION_EVERY steps - ADVICE r05; without a data-parallel group it reads the clock)
@@ -311,6 +312,11 @@ class Estimator:
             n += 1
         for h in all_hooks:
             h.end(None)
+            # data-parallel evaluation: the hook has summed the ranks' loss shares (one reduction per evaluation) - the global loss, the
+            # same on every rank, in place of this rank's own
+            g = getattr(h, 'eval_global_loss_sum', None)
+            if g is not None:
+                loss_sum = g
         ds.close()
         self._check_device_health(collective=False)
         out = {k: (v.result() if hasattr(v, 'result') else v) for k, v in spec.eval_metric_ops.items()}

@@ -130,6 +130,32 @@ class NDCG(StreamingMetric):
         return np.mean(self.ndcg_results)
 
 
+def accuracy_from_rank_hist(hist, pop_sum, topn):
+    """HitRate@n, MRR@n, NDCG@n and HitRate-by-session-position from the rank histogram of cham_eval_rank_hist: ``hist[t, r]`` =
+    valid clicks at session position t whose positive ranked r (0-based; ranks >= topn share bin ``topn``), ``pop_sum[t]`` = fp64 sum
+    of the labels' recent normalised popularity at t (or None).  Same keys and result shapes as the streaming classes above, all
+    arithmetic fp64.  Equal to them because the sampler removes every id of a session, its labels included, from that session's
+    negatives: the label occurs exactly once in its candidate row, so its rank decides every one of these metrics (the ideal DCG of
+    a single relevant item is 1)."""
+    hist = np.asarray(hist, dtype=np.int64)[:, :topn + 1]
+    by_rank = hist.sum(axis=0)
+    total = int(by_rank.sum())
+    ranks = np.arange(topn, dtype=np.float64)
+    top = by_rank[:topn].astype(np.float64)
+    per_pos = hist.sum(axis=1)
+    hits_pos = hist[:, :topn].sum(axis=1)
+    pop = np.zeros(hist.shape[0], np.float64) if pop_sum is None else np.asarray(pop_sum, dtype=np.float64)
+    cols = [int(t) for t in np.flatnonzero(per_pos)]
+    tot = {t + 1: int(per_pos[t]) for t in cols}
+    hitrate = {t + 1: int(hits_pos[t]) / float(per_pos[t]) for t in cols}
+    avg_pop = {t + 1: float(pop[t]) / float(per_pos[t]) for t in cols}
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return {HitRate.name: int(by_rank[:topn].sum()) / float(total) if total else float('nan'),
+                MRR.name: (top / (ranks + 1.0)).sum() / np.float64(total),
+                NDCG.name: (top * _log_rank_discount(ranks)).sum() / np.float64(total),
+                HitRateBySessionPosition.name: (hitrate, avg_pop, tot)}
+
+
 class ItemCoverage(StreamingMetric):
     """|recommended items| / |clicked items|.  The clicked set is seeded with the recent-clicks buffer given at construction (a 0
     included while the buffer has empty slots), then grows by the non-zero labels and clicked items of each batch; the

@@ -825,6 +825,8 @@ class NARModuleModel:
         self._eval = None
         self._ba = None                        # enable_beyond_accuracy_metrics: launch scalars; _ba_buffers: maps, counts, per-click values
         self._ba_buffers = None
+        self._rh = None                        # enable_rank_histogram: the device record of cham_eval_rank_hist
+        self.dp = None                         # parallel.DataParallelNAR.attach: the data-parallel wrapper this model's batches go through
         # attributes ItemsStateUpdaterHook fetches / feeds (nar_model.py:1435-1467)
         inp = lambda k: Tensor(k, lambda: np.asarray(self.inputs[k]))
         self.item_clicked = inp('item_clicked')
@@ -879,6 +881,13 @@ class NARModuleModel:
             buffer=torch.from_numpy(buf).to(dev, non_blocking=True),
             pop_norm=torch.from_numpy(np.ascontiguousarray(pop_norm, dtype=np.float32)).to(dev, non_blocking=True),
             last=torch.from_numpy(np.ascontiguousarray(nz)).to(dev, non_blocking=True), n_last=int(nz.shape[0]))
+
+    def upload_current(self, features, labels):
+        """How a batch of the input stream reaches the device: this rank's row shard of it (with the global integers and ``row_begin``)
+        under an attached data-parallel wrapper, the whole batch otherwise."""
+        if self.dp is not None:
+            return self.dp.upload(features, labels)
+        return self.upload_batch(features, labels)
 
     def upload_batch(self, features, labels, global_features=None, global_labels=None, row_begin=0):
         """numpy batch (input_fn output) -> device tensors + the few host scalars the launch parameters need."""
@@ -1515,8 +1524,9 @@ class NARModuleModel:
         nxt = dataset.peek()
         if nxt is None:
             return
-        d = self.upload_batch(nxt[0], nxt[1])
-        self.presample(d)
+        d = self.upload_current(nxt[0], nxt[1])
+        if not d.get('empty'):
+            self.presample(d)
         self._staged = (nxt[0]['item_clicked'], d)
 
     def train_step(self, device_batch=None):
@@ -1527,7 +1537,9 @@ class NARModuleModel:
             if staged is not None and staged[0] is self.inputs['item_clicked']:        # the very arrays stage_next() uploaded
                 d = staged[1]
             else:
-                d = self.upload_batch(self.inputs, self.labels)
+                d = self.upload_current(self.inputs, self.labels)
+        if d.get('empty'):
+            return self._empty_shard_train_step(d)
         with _roctx.range_("NAR step: forward (K0 sampler .. loss)"):        # (CHAM_ROCTX=1: roctx ranges for rocprofv3 --marker-trace)
             self._defer_loss = True          # the loss record may finish on the side lane: backward() joins it
             try:
@@ -1541,6 +1553,35 @@ class NARModuleModel:
         with _roctx.range_("NAR step: exchange + L2 + TF-Adam"):
             self.apply_gradients()
         return self.total_loss
+
+    def _empty_shard_train_step(self, d):
+        """The optimizer step of a data-parallel rank whose row shard of the global batch is EMPTY (fewer sessions than ranks: the last batch
+        of a file chunk): no forward, no backward and no kernel over zero rows - a zero gradient buffer and a zero loss share, then the same
+        exchange (the early bucket included: every rank issues the same collectives in the same order) and the same Adam as every other
+        rank.  ``d`` carries the global integers the replicated state update reads (parallel.DataParallelNAR.upload)."""
+        rt = self.rt
+        self._empty_shard_loss(d)
+        rt.grads.zero_()
+        if rt.dp_early_bucket is not None:
+            rt.dp_early_bucket(rt.grads)
+        with _roctx.range_("NAR step: exchange + L2 + TF-Adam"):
+            self.apply_gradients()
+        return self.total_loss
+
+    def _empty_shard_loss(self, d):
+        """Loss record [total, xe, reg] of a rank without rows of this batch: xe share 0, the L2 term of the (replicated) weights - the loss
+        kernels of forward() over ONE zero row in place of the batch's, so that nothing is launched over zero rows."""
+        rt, lib, s = self.rt, self.rt.lib, _stream()
+        self._d = d
+        if d.get('uploaded') is not None:      # (the replicated state update reads the global integers behind this stream)
+            torch.cuda.current_stream().wait_event(d['uploaded'])
+        if getattr(self, '_empty_loss', None) is None:
+            self._empty_loss = (torch.zeros(1, dtype=torch.float32, device=rt.device), torch.zeros(3, dtype=torch.float32, device=rt.device))
+        nll, loss = self._empty_loss
+        check(lib.cham_sumsq_partial(ptr(rt.flat), rt.layout.n_reg, ptr(rt.sumsq), s), "cham_sumsq_partial")
+        check(lib.cham_loss_finalize(ptr(nll), 1, float(d['sum_mask']), ptr(rt.sumsq), float(self.reg_weight_decay), ptr(loss), s),
+              "cham_loss_finalize")
+        self.total_loss = loss
 
     @staticmethod
     def eval_step_key(global_step, eval_iter):
@@ -1574,13 +1615,62 @@ class NARModuleModel:
     def evaluate_step(self, device_batch=None):
         """EVAL-mode ``session.run``: forward with the eval negative-sample counts (nar_trainer_gcom.py:240-242) +
         rank_items_by_predicted_prob (nar_model.py:777-794) [+ the beyond-accuracy metrics of the ranked lists]."""
-        d = device_batch if device_batch is not None else self.upload_batch(self.inputs, self.labels)
+        d = device_batch if device_batch is not None else self.upload_current(self.inputs, self.labels)
+        if d.get('empty'):       # a data-parallel rank without rows of this batch: nothing to rank, nothing added to the records
+            self._empty_shard_loss(d)
+            self._eval_iter += 1
+            return self.total_loss
         pl = self.forward(d)
         self._rank_items(pl, d)
+        if self._rh is not None:
+            self._rank_histogram(d)
         if self._ba is not None:
             self._beyond_accuracy(d)
         self._eval_iter += 1
         return self.total_loss
+
+    # ------------------------------------------------------------------ rank histogram of the evaluation (csrc/eval_metrics.hip)
+    def enable_rank_histogram(self, topn, t_cap):
+        """From now on every evaluate_step adds its clicks to a device record (cham_eval_rank_hist): hist int64 [t_cap, topn + 1] = valid
+        clicks by (session position, rank of the positive; ranks >= topn in the last bin) and pop_sum fp64 [t_cap] = sum of the labels'
+        recent normalised popularity by position.  HitRate@n, MRR@n, NDCG@n and HitRate-by-position follow from it
+        (metrics.accuracy_from_rank_hist); integer, so the records of data-parallel ranks add up exactly.  Allocates and zeroes the record."""
+        if not 1 <= topn <= 256:
+            raise ValueError("the rank histogram needs 1 <= eval_metrics_top_n <= 256 (got %d)" % topn)
+        if t_cap < 1:
+            raise ValueError("t_cap must be >= 1")
+        dev = self.rt.device
+        self._rh = dict(topn=int(topn), t_cap=int(t_cap), hist=torch.zeros(int(t_cap), int(topn) + 1, dtype=torch.int64, device=dev),
+                        pop_sum=torch.zeros(int(t_cap), dtype=torch.float64, device=dev))
+
+    def reserve_rank_histogram(self, T):
+        """Make room for batches of T click positions (a longer record, the counts so far kept).  Data-parallel ranks call this with the
+        GLOBAL batch's T for every batch, the ranks without rows included: their records have one shape when they are summed."""
+        rh = self._rh
+        if T > rh['t_cap']:
+            t_cap = max(int(T), 2 * rh['t_cap'])
+            hist = torch.zeros(t_cap, rh['topn'] + 1, dtype=torch.int64, device=self.rt.device)
+            pop_sum = torch.zeros(t_cap, dtype=torch.float64, device=self.rt.device)
+            hist[:rh['t_cap']].copy_(rh['hist'])
+            pop_sum[:rh['t_cap']].copy_(rh['pop_sum'])
+            rh.update(t_cap=t_cap, hist=hist, pop_sum=pop_sum)
+
+    def _rank_histogram(self, d):
+        """This eval step's label ranks (after _rank_items: in a compacted batch after the scatter back into [B, T], padded positions -1)
+        into the record, on the current stream; pop_norm = the array this batch was fed."""
+        rh, ev, st = self._rh, self._eval, self._dev_state
+        B, T = ev['label_rank'].shape
+        if T > rh['t_cap']:
+            raise ValueError("evaluation batch of %d click positions: the rank histogram was enabled for %d" % (T, rh['t_cap']))
+        check(self.rt.lib.cham_eval_rank_hist(ptr(ev['label_rank']), ptr(d['label_next']), B, T, rh['topn'], ptr(st['pop_norm']),
+                                              self.rt.n_items, ptr(rh['hist']), ptr(rh['pop_sum']), rh['t_cap'], _stream()),
+              "cham_eval_rank_hist")
+        if st.get('device'):
+            self.articles_recent_pop_norm.note_consumed(d['aci'])      # pop_norm is read up to here: the state update waits for this
+
+    def rank_histogram(self):
+        """(hist [t_cap, topn + 1] int64, pop_sum [t_cap] float64) as numpy: what the evaluate_steps since enable_rank_histogram added."""
+        return self._rh['hist'].cpu().numpy(), self._rh['pop_sum'].cpu().numpy()
 
     # ------------------------------------------------------------------ beyond-accuracy evaluation metrics (csrc/eval_metrics.hip)
     def enable_beyond_accuracy_metrics(self, topn, relevance_positive_sample, relevance_negative_samples, recent_clicks_buffer):
@@ -1603,6 +1693,9 @@ class NARModuleModel:
         ba['seed'] = buf                          # (kept alive until the seed launch has run)
         check(lib.cham_eval_coverage_seed(ptr(buf), buf.numel(), n_items, ptr(ba['rec']), ptr(ba['clk']), _stream()),
               "cham_eval_coverage_seed")
+        # data parallel: fp64 column sums of the per-click values and the number of valid clicks, over this rank's rows of every batch
+        ba['sums'] = torch.zeros(4, dtype=torch.float64, device=rt.device)
+        ba['clicks'] = torch.zeros(1, dtype=torch.int64, device=rt.device)
         self._ba = dict(topn=int(topn), rel_pos=float(relevance_positive_sample), rel_neg=float(relevance_negative_samples))
 
     def _beyond_accuracy(self, d):
@@ -1621,6 +1714,17 @@ class NARModuleModel:
         if st.get('device'):
             self.articles_recent_pop_norm.note_consumed(d['aci'])      # pop_norm is read up to here: the state update waits for this
         self._ba_shape = (B, T)
+        if self.dp is not None:      # the rank's share of the evaluation's totals (per_click is 0 at padded positions); reduced once, in the hook's end()
+            ba['sums'] += ba['per_click'].double().sum(dim=0)
+            ba['clicks'] += (d['label_next'] != 0).sum()
+
+    def coverage_counts(self, rec_map=None, clk_map=None):
+        """(recommended, clicked) item counts of the coverage maps (default: this model's), one cham_eval_coverage_count + one read-back."""
+        rt, ba = self.rt, self._ba_buffers
+        rec, clk = (ba['rec'], ba['clk']) if rec_map is None else (rec_map, clk_map)
+        check(rt.lib.cham_eval_coverage_count(ptr(rec), ptr(clk), rt.n_items, ptr(ba['ws']), ba['ws'].numel(), ptr(ba['counts']), _stream()),
+              "cham_eval_coverage_count")
+        return tuple(ba['counts'].cpu().tolist())
 
     def beyond_accuracy_outputs(self):
         """(per_click [B, T, 4] float32 = ESI-R, ESI-RR, EILD-R, EILD-RR (0 at padded positions), (recommended, clicked) item counts
@@ -1809,6 +1913,9 @@ class ItemsStateUpdaterHook:
         item coverage, ESI-R / ESI-RR (novelty) and content EILD-R / EILD-RR (diversity, relevance of the negatives =
         ``eval_negative_sample_relevance``) from cham_eval_beyond_accuracy, which reads the ranked ids, the ACE matrix, the
         ``articles_recent_pop_norm`` this batch was fed and the coverage maps seeded from the recent-clicks buffer at begin().
+      * under an active data-parallel wrapper (``model.dp``, nar/parallel.py) an EVAL pass covers this rank's session rows of every batch:
+        the ranked lists stay on the device, the accuracy metrics come from the rank histogram (cham_eval_rank_hist), and end() reduces
+        every record over the ranks ONCE (DataParallelNAR.reduce_eval_records) - every rank logs the same, global numbers.
     Out of scope: the baseline recommenders (``eval_benchmark_classifiers`` must be empty), the
     co-occurrence matrix (:1650), the metrics the reference defines but does not instantiate."""
 
@@ -1850,6 +1957,19 @@ class ItemsStateUpdaterHook:
             if self.eval_metrics_by_session_position:
                 self.streaming_metrics.append(HitRateBySessionPosition(self.eval_metrics_top_n))
             self.stats_logs = []
+            if self._data_parallel():
+                # every rank evaluates its own rows of every batch: the accuracy metrics come from the device-side rank histogram, summed
+                # over the ranks once, in end() - the host classes above only fix the names and the order of the result keys
+                if self.eval_cold_start or self.sessions_negative_items_log is not None or self.sessions_chameleon_recommendations_log is not None:
+                    raise ValueError("eval_cold_start / save_eval_sessions_negative_samples / save_eval_sessions_recommendations need every "
+                                     "rank's ranked lists on one host: not available in a data-parallel evaluation")
+                self.model.enable_rank_histogram(self.eval_metrics_top_n, 32)
+                self._dp_loss = torch.zeros(3, dtype=torch.float64, device=self.model.rt.device)
+                self.eval_global_loss_sum = None
+
+    def _data_parallel(self):
+        dp = getattr(self.model, 'dp', None)
+        return dp is not None and dp.active
 
     def after_create_session(self, session=None, coord=None):
         pass
@@ -1860,7 +1980,11 @@ class ItemsStateUpdaterHook:
         fetches = {'clicked_items': m.item_clicked, 'clicked_timestamps': m.event_timestamp,
                    'next_item_labels': m.next_item_label, 'last_item_label': m.label_last_item,
                    'session_id': m.session_id, 'user_id': m.user_id}
-        if self.eval_cold_start or self.mode == ModeKeys.EVAL:                 # nar_model.py:1444
+        dp_eval = self.mode == ModeKeys.EVAL and self._data_parallel()
+        if dp_eval:      # the ranked lists stay on the device (a rank without rows of this batch has none)
+            fetches.update(batch_items_count=m.batch_items_count, batch_unique_items_count=m.batch_unique_items_count)
+            m.reserve_rank_histogram(np.asarray(m.inputs['item_clicked']).shape[1])
+        elif self.eval_cold_start or self.mode == ModeKeys.EVAL:               # nar_model.py:1444
             fetches.update(predicted_item_ids=m.predicted_item_ids, eval_batch_negative_items=m.batch_negative_items,
                            batch_items_count=m.batch_items_count, batch_unique_items_count=m.batch_unique_items_count,
                            predicted_item_probs=m.predicted_item_probs, label_rank=m.label_rank)
@@ -1879,7 +2003,13 @@ class ItemsStateUpdaterHook:
         clicked_timestamps = np.squeeze(r['clicked_timestamps'], axis=-1)
         next_item_labels, last_item_label = r['next_item_labels'], r['last_item_label']
         sessions_ids = r['session_id']
-        if self.mode == ModeKeys.EVAL:
+        if self.mode == ModeKeys.EVAL and self._data_parallel():
+            # the inputs are the GLOBAL batch on every rank: these counts are global as they stand
+            self.stats_logs.append({'batch_items_count': r['batch_items_count'],
+                                    'batch_unique_items_count': r['batch_unique_items_count'],
+                                    'batch_sessions_count': len(sessions_ids)})
+            self._dp_loss += self.model.total_loss.double()      # [total, xe share, L2] of this rank's rows (device add, no read-back)
+        elif self.mode == ModeKeys.EVAL:
             predicted_item_ids = r['predicted_item_ids']
             # TF streaming twins (sparse_recall_at_top_k, define_mrr_metric) from the device-side rank of the positive
             rank = r['label_rank']
@@ -1946,7 +2076,48 @@ class ItemsStateUpdaterHook:
         st.get_cold_start_state().update_items_num_steps_before_first_rec(predicted_top_item_ids, st.items_first_click_step,
                                                                           st.get_current_step())
 
+    def _reduce_data_parallel_eval(self):
+        """The evaluation's records of this rank's rows -> global results, identical on every rank: ONE reduce_eval_records (int64 rank
+        histogram and click count, fp64 popularity / beyond-accuracy / loss sums; MAX-union of the coverage maps)."""
+        from .evaluation import compute_metrics_results
+        from .metrics import HitRate, HitRateBySessionPosition, MRR, NDCG, accuracy_from_rank_hist
+        m, dp, n = self.model, self.model.dp, self.eval_metrics_top_n
+        ba = m._ba_buffers if self.eval_beyond_accuracy_metrics else None
+        sums = self._dp_loss if ba is None else torch.cat([self._dp_loss, ba['sums']])
+        red = dp.reduce_eval_records(m._rh['hist'], m._rh['pop_sum'], counts=None if ba is None else ba['clicks'], sums=sums,
+                                     rec_map=None if ba is None else ba['rec'], clk_map=None if ba is None else ba['clk'])
+        hist = red['hist'].cpu().numpy()
+        acc = accuracy_from_rank_hist(hist, red['pop_sum'].cpu().numpy(), n)
+        sums = red['sums'].cpu().numpy()
+        # loss: xe shares summed over ranks + the L2 term every rank reports (summed world times)
+        self.eval_global_loss_sum = float(sums[1] + sums[2] / dp.world)
+        total, hits = int(hist.sum()), int(hist[:, :n].sum())
+        if 'hitrate_at_n' in self.eval_metric_ops:
+            self.eval_metric_ops['hitrate_at_n'].update(hits, total)
+        if 'mrr_at_n' in self.eval_metric_ops:
+            self.eval_metric_ops['mrr_at_n'].update(acc[MRR.name] * total if total else 0.0, total)
+        self.eval_streaming_metrics_last = {k: v.result() for k, v in self.eval_metric_ops.items()}
+        values = {HitRate.name: acc[HitRate.name], MRR.name: acc[MRR.name], NDCG.name: acc[NDCG.name],
+                  HitRateBySessionPosition.name: acc[HitRateBySessionPosition.name]}
+        if ba is not None:
+            rec, clk = red['coverage_counts']
+            values[ItemCoverage.name] = rec / float(clk)
+            clicks = int(red['counts'].cpu()[0])
+            for k, cls in enumerate(BEYOND_ACCURACY_PER_CLICK):
+                values[cls.name] = float(sums[3 + k]) / clicks if clicks else float('nan')
+
+        class _Reduced:
+            def __init__(self, name):
+                self.name = name
+
+            def result(self):
+                return values[self.name]
+        self.eval_streaming_metrics_last.update(compute_metrics_results([_Reduced(x.name) for x in self.streaming_metrics],
+                                                                        recommender='chameleon'))
+
     def end(self, session=None):
+        if self.mode == ModeKeys.EVAL and self._data_parallel():
+            self._reduce_data_parallel_eval()
         if self.mode == ModeKeys.EVAL:                                         # :1669-1695
             self.eval_streaming_metrics_last['clicks_count'] = int(np.sum([x['batch_items_count'] for x in self.stats_logs]))
             self.eval_streaming_metrics_last['sessions_count'] = int(np.sum([x['batch_sessions_count'] for x in self.stats_logs]))

@@ -213,6 +213,10 @@ def nar_module_model_fn(features, labels, mode, params):
                            internal_features_config=internal_features_config, eval_cold_start=params['eval_cold_start'],
                            rnn_cell=params.get('rnn_cell', 'ugrnn'), gemm_dtype=params.get('gemm_dtype', 'f32'),
                            recommendations_ranking=params.get('recommendations_ranking', 'mlp'))
+    # under `python -m torch.distributed.run` (parallel.init_from_env): this rank's row shard of every batch, gradients summed over the ranks,
+    # evaluation records reduced once per evaluate().  ONE wrapper per runtime, re-pointed at the model of this call.
+    from .parallel import attach_data_parallel
+    attach_data_parallel(model)
     state = params.get('clicked_items_state') or clicked_items_state
     metrics_log = params.get('eval_sessions_metrics_log', eval_sessions_metrics_log)
     eval_metrics = {'hitrate_at_n': StreamingMean(), 'mrr_at_n': StreamingMean()} if mode == ModeKeys.EVAL else {}
@@ -283,6 +287,33 @@ def train_and_evaluate_loop(flags, ace, articles_metadata, articles_features_con
     FLAGS = flags
     if FLAGS.use_local_cache_model_dir or FLAGS.warmup_model_dir:
         raise NotImplementedError("GCS model-dir caching / warm start download is out of scope (copy model.ckpt.pt into --model_dir)")
+    import torch.distributed as dist
+    from .parallel import init_from_env
+    had_group = dist.is_initialized()
+    rank, world = init_from_env()
+    try:
+        return _train_and_evaluate_loop(rank, world, ace, articles_metadata, articles_features_config, session_features_config, state_cls)
+    finally:
+        if world > 1 and not had_group and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+_DATA_PARALLEL_REFUSED_FLAGS = ('eval_cold_start', 'save_eval_sessions_negative_samples', 'save_eval_sessions_recommendations')
+
+
+def _train_and_evaluate_loop(rank, world, ace, articles_metadata, articles_features_config, session_features_config, state_cls):
+    """The loop on one rank of `world`.  --batch_size is the GLOBAL batch; every rank reads every file (the step feeds every rank the global
+    batch's integers) and trains / evaluates its own session rows of each batch.  Rank 0 alone writes the metrics CSV (every rank holds the
+    same numbers) and prints the INFO lines; the Estimator writes the checkpoint on rank 0."""
+    global clicked_items_state, eval_sessions_metrics_log, sessions_negative_items_log
+    global sessions_chameleon_recommendations_log, global_eval_hour_id
+    if world > 1:
+        for flag in _DATA_PARALLEL_REFUSED_FLAGS:
+            if getattr(FLAGS, flag, False):
+                raise ValueError("--%s needs every rank's ranked lists on one host: not supported under data parallelism (WORLD_SIZE=%d)"
+                                 % (flag, world))
+    chief = rank == 0
+    info = (lambda *a, **k: print(*a, **k)) if chief else (lambda *a, **k: None)
     np.random.seed(RANDOM_SEED)
     os.makedirs(FLAGS.model_dir, exist_ok=True)
     ace = l2_normalize_rows(ace) * np.float32(FLAGS.content_embedding_scale_factor)
@@ -299,7 +330,7 @@ def train_and_evaluate_loop(flags, ace, articles_metadata, articles_features_con
     if FLAGS.train_files_from > FLAGS.train_files_up_to:
         raise Exception('Final training file cannot be lower than Starting training file')
     train_files = train_files[FLAGS.train_files_from:FLAGS.train_files_up_to + 1]
-    print('INFO:{} files where the network will be trained and evaluated on, from {} to {}'.format(
+    info('INFO:{} files where the network will be trained and evaluated on, from {} to {}'.format(
         len(train_files), train_files[0], train_files[-1]), flush=True)
     start_train = time()
     training_files_chunks = list(chunks(train_files, FLAGS.training_hours_for_each_eval))
@@ -307,14 +338,14 @@ def train_and_evaluate_loop(flags, ace, articles_metadata, articles_features_con
                                                                truncate_session_length=FLAGS.truncate_session_length))
     for chunk_id in range(0, len(training_files_chunks) - 1):
         chunk = training_files_chunks[chunk_id]
-        print('INFO:Training files from {} to {}'.format(chunk[0], chunk[-1]), flush=True)
+        info('INFO:Training files from {} to {}'.format(chunk[0], chunk[-1]), flush=True)
         model.train(input_fn=input_fn(chunk))
         eval_file = training_files_chunks[chunk_id + 1][0]
-        print('INFO:Evaluating file {}'.format(eval_file), flush=True)
+        info('INFO:Evaluating file {}'.format(eval_file), flush=True)
         res = model.evaluate(input_fn=input_fn(eval_file))
-        print('INFO:eval {}'.format({k: (round(float(v), 5) if isinstance(v, (float, np.floating)) else v) for k, v in res.items()}),
+        info('INFO:eval {}'.format({k: (round(float(v), 5) if isinstance(v, (float, np.floating)) else v) for k, v in res.items()}),
               flush=True)
-        if chunk_id % FLAGS.save_results_each_n_evals == 0:
+        if chunk_id % FLAGS.save_results_each_n_evals == 0 and chief:
             save_eval_benchmark_metrics_csv(eval_sessions_metrics_log, FLAGS.model_dir, FLAGS.training_hours_for_each_eval)
             if FLAGS.save_eval_sessions_negative_samples:
                 _append_json_lines(os.path.join(FLAGS.model_dir, 'eval_sessions_negative_samples.json'), sessions_negative_items_log)
@@ -324,13 +355,14 @@ def train_and_evaluate_loop(flags, ace, articles_metadata, articles_features_con
                                    [dict(eval_hour_id=global_eval_hour_id, **r) for r in sessions_chameleon_recommendations_log])
                 sessions_chameleon_recommendations_log.clear()
                 global_eval_hour_id += 1
-    save_eval_benchmark_metrics_csv(eval_sessions_metrics_log, FLAGS.model_dir, FLAGS.training_hours_for_each_eval)
+    if chief:
+        save_eval_benchmark_metrics_csv(eval_sessions_metrics_log, FLAGS.model_dir, FLAGS.training_hours_for_each_eval)
     if FLAGS.save_eval_sessions_negative_samples:
         _append_json_lines(os.path.join(FLAGS.model_dir, 'eval_sessions_negative_samples.json'), sessions_negative_items_log)
     if FLAGS.save_eval_sessions_recommendations:
         _append_json_lines(os.path.join(FLAGS.model_dir, 'eval_chameleon_recommendations_log.json'),
                            [dict(eval_hour_id=global_eval_hour_id, **r) for r in sessions_chameleon_recommendations_log])
-    print('INFO:==== Finalized TRAINING Loop elapsed {:.1f} minutes'.format((time() - start_train) / 60.0), flush=True)
+    info('INFO:==== Finalized TRAINING Loop elapsed {:.1f} minutes'.format((time() - start_train) / 60.0), flush=True)
     return model
 
 

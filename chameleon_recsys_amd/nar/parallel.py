@@ -8,7 +8,9 @@ for its own rows only (negative sampling is keyed by the GLOBAL row index, so th
 sharding), and the flat gradient buffer is summed with ONE all-reduce per step (dense grads ~12 MB + the small
 embedding tables; CHAM_DP_MODE=sharded reduce-scatters the whole buffer to owner ranks instead, =sparse / sparse_rs exchange only
 the touched rows of the item table - see DataParallelNAR).  The state update after the step is applied identically on every rank from the
-replicated ids - no communication.
+replicated ids - no communication.  Evaluation shards the same way; its per-rank records (rank histogram, popularity and
+beyond-accuracy sums, coverage maps, loss shares) are reduced ONCE per evaluation (reduce_eval_records).  The trainers reach all of this
+through init_from_env() / attach_data_parallel(model) under `python -m torch.distributed.run`.
 """
 import logging
 
@@ -28,6 +30,42 @@ def slice_batch(features, labels, begin, end):
     f = {k: np.asarray(v)[begin:end] for k, v in features.items()}
     l = {k: np.asarray(v)[begin:end] for k, v in labels.items()}
     return f, l
+
+
+def init_from_env():
+    """(rank, world) of this process under ``python -m torch.distributed.run`` (WORLD_SIZE, RANK, LOCAL_RANK): with a world of 1 nothing
+    happens; otherwise the device is set and the default process group initialised - backend CHAM_DIST_BACKEND (default "nccl" = RCCL,
+    one rank per GPU; "gloo" puts several ranks on one GPU: local_rank % device_count) - unless a group already exists (idempotent)."""
+    import os
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world == 1:
+        return 0, 1
+    if dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    backend = os.environ.get("CHAM_DIST_BACKEND", "nccl")
+    if torch.cuda.is_available():
+        if backend != "nccl":
+            local_rank = local_rank % torch.cuda.device_count()
+        torch.cuda.set_device(local_rank)
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    if backend == "nccl":
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+    else:
+        dist.init_process_group(backend)
+    return dist.get_rank(), dist.get_world_size()
+
+
+def attach_data_parallel(model):
+    """The data-parallel wrapper of ``model``'s runtime when the default process group has more than one rank (else None).  There is ONE
+    wrapper per runtime: the first call creates it (the initial-weights broadcast runs then, once), later calls - a model_fn builds a new
+    model per train / evaluate call around the persistent runtime - re-point it at the new model."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return None
+    dp = getattr(model.rt, 'dp', None)
+    if dp is None:
+        dp = DataParallelNAR(model)
+    return dp.attach(model)
 
 
 class DataParallelNAR:
@@ -67,6 +105,7 @@ class DataParallelNAR:
         rt.dp_rank, rt.dp_world = self.rank, self.world
         rt.dp_pg = process_group
         rt.dp_mode = self.mode
+        rt.dp = self                       # one wrapper per runtime (attach_data_parallel)
         self._early, self._early_work, self._early_bytes = None, None, 0
         # dtype of the dense gradient exchange ("12-13 MB fp32 / 6.5 MB bf16"): CHAM_DP_GRAD_DTYPE = f32 | bf16 | auto
         # (default: bf16 exactly when the runtime computes in bf16 - BASELINE configs[2]).  bf16: the flat gradients are rounded to bf16
@@ -366,12 +405,84 @@ class DataParallelNAR:
         self._all_gather(flat_params, flat_params[a:a + n].clone())
         self.last_exchange_bytes = 4 * flat_grads.numel() + 4 * flat_params.numel()
 
+    def attach(self, model):
+        """Point the wrapper at ``model`` (another model around the same runtime) and make it the way that model's batches reach the
+        device (NARModuleModel.upload_current)."""
+        if model.rt is not self.model.rt:
+            raise ValueError("a DataParallelNAR belongs to one runtime: the model was built around another")
+        self.model = model
+        model.dp = self
+        return self
+
     def upload(self, global_features, global_labels):
         n = np.asarray(global_features['item_clicked']).shape[0]
         b, e = shard_rows(n, self.rank, self.world)
+        if n < self.world and self.active:
+            # a global batch of fewer sessions than ranks (the last batch of a file chunk): the ranks past the n-th have no rows.  Decided
+            # from n alone, so every rank takes the same branch.
+            if self.mode in ("sparse", "sparse_rs"):
+                raise ValueError("a global batch of %d sessions on %d ranks leaves ranks without rows: the touched-rows list of CHAM_DP_MODE=%s "
+                                 "comes from the step's own sampler call; use the allreduce or sharded mode" % (n, self.world, self.mode))
+            if e == b:
+                return self._upload_empty(global_features, global_labels, b)
         f, l = slice_batch(global_features, global_labels, b, e)
         # sequence tensors keep the GLOBAL padded length T (every rank must agree on T for the sampler keys)
         return self.model.upload_batch(f, l, global_features, global_labels, row_begin=b)
+
+    def _upload_empty(self, gf, gl, row_begin):
+        """What a rank WITHOUT rows of this global batch needs on the device: the global integers the replicated state update reads, and
+        the host scalars.  The model runs neither forward nor backward on it (NARModuleModel._empty_shard_train_step, evaluate_step)."""
+        ic = np.asarray(gf['item_clicked'], np.int64)
+        g_ssz = np.asarray(gf['session_size'], dtype=np.int64).reshape(-1)
+        host = dict(aci=np.concatenate([ic, np.asarray(gl['label_last_item'], np.int64).reshape(-1, 1)], 1),
+                    g_event_ts=np.ascontiguousarray(gf['event_timestamp'], dtype=np.int64))
+        d = dict(B=0, T=ic.shape[1], Bg=ic.shape[0], row_begin=row_begin, empty=True,
+                 sum_mask=float(np.minimum(np.maximum(g_ssz - 1, 0), ic.shape[1]).sum()), max_ts=int(host['g_event_ts'].max()))
+        d.update(self.model._h2d(host))
+        return d
+
+    # ---- evaluation: the per-rank records of an evaluate() call -> global records, identical on every rank
+    def _reduce(self, t, op):
+        """In-place all-reduce of any tensor: RCCL takes it as it is; on another backend a device tensor goes through a host copy."""
+        self.collective_calls["all_reduce"] += 1
+        if t.is_cuda and dist.get_backend(self.pg) != "nccl":
+            h = t.cpu()
+            dist.all_reduce(h, op=op, group=self.pg)
+            t.copy_(h)
+        else:
+            dist.all_reduce(t, op=op, group=self.pg)
+
+    def reduce_eval_records(self, hist, pop_sum, counts=None, sums=None, rec_map=None, clk_map=None):
+        """ONCE per evaluation (the hook's end()): every rank's records of its own rows -> the global records, on every rank.
+          hist int64 [t_cap, topn + 1], pop_sum fp64 [t_cap]     the rank histogram (cham_eval_rank_hist)             SUM
+          counts int64 [k] / sums fp64 [m] (optional)            click / session counts; beyond-accuracy column sums,  SUM
+                                                                 loss shares
+          rec_map / clk_map uint8 [n_items] (optional)           the coverage maps: union                              MAX, in place
+        The integers travel packed in one int64 collective and the fp64 sums in another: int64 sums are exact, fp64 sums are added in the
+        collective's rank order, identically for every rank.  Returns dict(hist, pop_sum, counts, sums[, coverage_counts = (recommended,
+        clicked) from ONE cham_eval_coverage_count over the united device maps]); the inputs other than the maps are not modified."""
+        out = {}
+        ints = [hist.reshape(-1)] + ([counts.reshape(-1)] if counts is not None else [])
+        flts = [pop_sum.reshape(-1)] + ([sums.reshape(-1)] if sums is not None else [])
+        for parts, dtype, names in ((ints, torch.int64, ('hist', 'counts')), (flts, torch.float64, ('pop_sum', 'sums'))):
+            if any(p.dtype != dtype for p in parts):
+                raise TypeError("reduce_eval_records: %s must be %s" % (" / ".join(names[:len(parts)]), dtype))
+            packed = torch.cat(parts)
+            if self.active:
+                self._reduce(packed, dist.ReduceOp.SUM)
+            n0 = parts[0].numel()
+            out[names[0]] = packed[:n0].view(hist.shape if dtype == torch.int64 else pop_sum.shape)
+            out[names[1]] = packed[n0:] if len(parts) > 1 else None
+        if (rec_map is None) != (clk_map is None):
+            raise ValueError("reduce_eval_records: both coverage maps or neither")
+        if rec_map is not None:
+            if self.active:
+                self._reduce(rec_map, dist.ReduceOp.MAX)
+                self._reduce(clk_map, dist.ReduceOp.MAX)
+            if rec_map.is_cuda:
+                out['coverage_counts'] = self.model.coverage_counts(rec_map, clk_map)
+        self.collective_calls["eval_reduce"] = self.collective_calls.get("eval_reduce", 0) + 1
+        return out
 
     def global_loss(self):
         """[total, xe, reg]: xe summed over ranks (each rank holds its rows' share / global sum(mask))."""

@@ -610,6 +610,15 @@ int cham_eval_coverage_seed(const int64_t* buffer_ids, int n_buf, int64_t n_item
 size_t cham_eval_coverage_workspace_bytes(int64_t n_items);
 int cham_eval_coverage_count(const uint8_t* rec_map, const uint8_t* clk_map, int64_t n_items, void* workspace, size_t workspace_bytes,
                              int64_t* counts, void* stream);
+/* Rank histogram of an evaluation step: label_rank [B, T] int32 from cham_rank_items (0-based rank of the positive among the 1 + N
+ * candidates, -1 at padded positions), labels [B, T].  For each position t < T and each row b, ascending, with label_rank[b,t] = r >= 0:
+ *   hist[t][min(r, topn)] += 1;   pop_sum[t] += (double)pop_norm[labels[b,t]]   (pop_norm given and 0 <= label < n_items only)
+ * hist int64 [t_cap][topn + 1] and pop_sum fp64 [t_cap] ACCUMULATE across launches (the caller zeroes them); rows t >= T are not touched;
+ * pop_norm NULL: pop_sum is not touched.  One writer per element and launch, fixed fp64 summation order, no float atomics: two runs are
+ * bit-identical.  HitRate@n, MRR@n, NDCG@n and HitRate-by-position follow from hist on the host (nar/metrics.accuracy_from_rank_hist).
+ * NULL label_rank / labels / hist / pop_sum, B, T or topn < 1, topn > 256, T > t_cap: -EINVAL, nothing launched. */
+int cham_eval_rank_hist(const int32_t* label_rank, const int64_t* labels, int B, int T, int topn, const float* pop_norm, int64_t n_items,
+                        int64_t* hist, double* pop_sum, int t_cap, void* stream);
 
 /* --- ACR module: the CNN article encoder (reference acr_module/acr/acr_model.py:83-87 embedding_lookup of the constant word-embedding
  * matrix, :272-289 cnn_feature_extractor, :196-198 weighted sparse softmax cross-entropy, :171 argmax), csrc/acr.hip.
