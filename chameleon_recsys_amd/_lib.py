@@ -112,6 +112,12 @@ _SIGNATURES = {
     "cham_mulpred_bwd": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
     "cham_score_softmax_fwd": (c_int, [P, c_int, P, P, c_int, c_int, c_float, P, P, P, P, c_float, P, P, P, P]),
     "cham_score_softmax_bwd": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, c_float, P, P, c_float, P, P, P, P, P]),
+    "cham_score_rankloss_fwd": (c_int, [P, c_int, P, P, c_int, c_int, c_float, P, P, P, P, c_float, P, P, P, c_int, c_float, P, P]),
+    "cham_score_rankloss_fwd_b16": (c_int, [P, c_int, P, P, c_int, c_int, c_float, P, P, P, P, c_float, P, P, P, c_int, c_float, P, P]),
+    "cham_score_rankloss_bwd": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, c_float, P, P, c_float, P, P, P, P, c_int, c_float, P, P]),
+    "cham_score_rankloss_bwd_b16": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, c_float, P, P, c_float, P, P, P, P, c_int, c_float, P, P]),
+    "cham_score_rankloss_bwd_dev": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, P, P, P, c_float, P, P, P, P, c_int, c_float, P, P]),
+    "cham_score_rankloss_bwd_b16_dev": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, P, P, P, c_float, P, P, P, P, c_int, c_float, P, P]),
     "cham_diversity_fwd": (c_int, [P, P, P, P, c_int, c_int, P, c_int, c_int, c_int64, c_float, P, P, P, P]),
     "cham_diversity_bwd": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, P, c_float, P, P, c_float, P, P, P]),
     "cham_diversity_bwd_b16": (c_int, [P, c_int, P, P, P, c_int, c_int, c_float, P, c_float, P, P, c_float, P, P, P]),

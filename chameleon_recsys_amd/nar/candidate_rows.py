@@ -53,6 +53,7 @@ class F32Rows:
     planes = False          # Z1 / dZ2 candidate rows live as planes (schedule: the W2 weight gradient is a plane GEMM + the clicked rows)
     b16 = False             # bf16-resident (schedule: which batches enqueue the critical chain first; the W2 wgrad runs beside the CAR dgrad)
     softmax_fwd, softmax_bwd = 'cham_score_softmax_fwd', 'cham_score_softmax_bwd'      # entry points that read this arm's S3 (bwd: + '_dev')
+    rankloss_fwd, rankloss_bwd = 'cham_score_rankloss_fwd', 'cham_score_rankloss_bwd'   # ... under a pairwise ranking loss (--loss_function; csrc/rank_loss.hip)
     diversity_bwd = 'cham_diversity_bwd'                                               # ... and the one that runs behind softmax_bwd (--diversity_reg_factor)
 
     def __init__(self, rt):
@@ -356,6 +357,7 @@ class Bf16Rows(F32Rows):
     # clicked-input rows stay fp32 (they feed / come from the fp32 recurrent branch)
     b16 = True
     softmax_fwd, softmax_bwd = 'cham_score_softmax_fwd_b16', 'cham_score_softmax_bwd_b16'
+    rankloss_fwd, rankloss_bwd = 'cham_score_rankloss_fwd_b16', 'cham_score_rankloss_bwd_b16'
     diversity_bwd = 'cham_diversity_bwd_b16'
     SHADOWED = ('W2', 'Ws1', 'Ws2', 'Ws3')
 

@@ -35,6 +35,10 @@ class ModeKeys:                       # tf.estimator.ModeKeys
     PREDICT = 'infer'
 
 
+# --loss_function: the value -> the `loss_kind` of cham_score_rankloss_* (csrc/rank_loss.hip); 'softmax' runs cham_score_softmax_* instead
+LOSS_FUNCTIONS = ('softmax', 'bpr', 'top1', 'bpr_max', 'top1_max')
+
+
 # Raw handle (hipStream_t as an int) of torch's current stream.  torch.cuda.current_stream() builds a Python Stream object (~8 us);
 # a step makes ~100 launches, and with short sessions the host's enqueue time is what bounds the boundary throughput - the private
 # C getters cost ~0.3 us.  (Fallback if a torch build lacks them.)
@@ -691,6 +695,7 @@ class StepPlan:
         self.nll = f32(BT)
         self.nov_aux = f32(BT, 3)
         self.div_sp = self.div_e = None       # --diversity_reg_factor > 0: S p [BT, NC] and p^T S p [BT] of the step (ensure_diversity)
+        self.rank_aux = None                  # --loss_function other than softmax: the loss's per-click record (ensure_rank_aux)
         self.mask = torch.zeros(BT, dtype=torch.uint8, device=dev)
         self.loss = torch.zeros(3, dtype=torch.float32, device=dev)
         # valid-position compaction (see NARModuleModel.upload_batch): compact copies of the sampler output, and the
@@ -733,6 +738,14 @@ class StepPlan:
             self.nbytes = self.allocated_bytes()
         return self.div_sp, self.div_e
 
+    def ensure_rank_aux(self):
+        """The per-click record a pairwise ranking loss carries from forward to backward ([BT, 8]; csrc/rank_loss.hip), allocated on the
+        first step of a model with a non-default --loss_function."""
+        if self.rank_aux is None:
+            self.rank_aux = torch.empty(self.BT, 8, dtype=torch.float32, device=self.probs.device)
+            self.nbytes = self.allocated_bytes()
+        return self.rank_aux
+
     def cand_Z1(self, P=None):
         """Candidate rows of the PreCAR output of the last step as fp32 [P * NC, C] (tests): the fp32 matrix, or the sum of its planes."""
         P = self.P if P is None else P
@@ -768,7 +781,8 @@ class NARModuleModel:
                  diversity_reg_factor=0.0,
                  internal_features_config={'recency': True, 'novelty': True, 'article_content_embeddings': True,
                                            'item_clicked_embeddings': True},
-                 eval_cold_start=False, runtime=None, rnn_cell='ugrnn', gemm_dtype='f32', recommendations_ranking='mlp'):
+                 eval_cold_start=False, runtime=None, rnn_cell='ugrnn', gemm_dtype='f32', recommendations_ranking='mlp',
+                 loss_function='softmax', bpr_max_reg=0.5):
         # log_base / log_1p bases of the recency and novelty features (nar_model.py:28-34, 1071-1075, 1148): launch scalars of the kernels
         for b in (elapsed_days_smooth_log_base, popularity_smooth_log_base):
             if not (b > 0.0) or b == 1.0:
@@ -780,6 +794,15 @@ class NARModuleModel:
         self.diversity_reg_factor = float(diversity_reg_factor)
         if not (self.diversity_reg_factor >= 0.0):
             raise ValueError("diversity_reg_factor must be >= 0")
+        # training objective over the [positive, N negatives] scores (--loss_function): 'softmax' = the reference's
+        # sampled softmax + NLL (csrc/scorer.hip), the others GRU4Rec's pairwise ranking losses (csrc/rank_loss.hip).  Not part of the
+        # parameter layout: a checkpoint written under one loss loads under another
+        if loss_function not in LOSS_FUNCTIONS:
+            raise ValueError("loss_function=%r: one of %s" % (loss_function, ', '.join(LOSS_FUNCTIONS)))
+        self.loss_function = loss_function
+        self.bpr_max_reg = float(bpr_max_reg)
+        if not (self.bpr_max_reg >= 0.0):
+            raise ValueError("bpr_max_reg must be >= 0")
         self.is_training = (mode == ModeKeys.TRAIN)
         if self.is_training and not (0.0 < keep_prob <= 1.0):
             raise ValueError("dropout_keep_prob must be in (0, 1]")
@@ -1187,13 +1210,17 @@ class NARModuleModel:
         _roctx.pop(); _roctx.push("K5 scorer, softmax, loss")
         if rt.cosine:      # cos(pred, candidate row), then the same kernel: its last-layer dot over (cos, 0, 0, 0) x (1, 0, 0, 0) returns cos (fp32 in every arm)
             arm.cosine_fwd(pl, s)
-            softmax_fwd, S3, K3, w4, b4 = 'cham_score_softmax_fwd', pl.cosq, 4, rt.cos_w4, rt.cos_b4
+            softmax_fwd, rankloss_fwd, S3, K3, w4, b4 = 'cham_score_softmax_fwd', 'cham_score_rankloss_fwd', pl.cosq, 4, rt.cos_w4, rt.cos_b4
         else:
             arm.scorer_fwd(pl, s)
-            softmax_fwd, S3, K3, w4, b4 = arm.softmax_fwd, pl.S3, 32, p('Ws4'), p('bs4')
-        check(getattr(lib, softmax_fwd)(ptr(S3), K3, ptr(w4), ptr(b4), BT, N, float(self.softmax_temperature),
-                                        ptr(pl.mask), ptr(pl.logits), ptr(pl.probs), ptr(pl.nll), self.novelty_reg_factor,
-                                        ptr(neg_ids), ptr(st['pop_norm']), ptr(pl.nov_aux), s), "cham_score_softmax_fwd")
+            softmax_fwd, rankloss_fwd, S3, K3, w4, b4 = arm.softmax_fwd, arm.rankloss_fwd, pl.S3, 32, p('Ws4'), p('bs4')
+        loss_args = (ptr(S3), K3, ptr(w4), ptr(b4), BT, N, float(self.softmax_temperature), ptr(pl.mask), ptr(pl.logits), ptr(pl.probs),
+                     ptr(pl.nll), self.novelty_reg_factor, ptr(neg_ids), ptr(st['pop_norm']), ptr(pl.nov_aux))
+        if self.loss_function == 'softmax':
+            check(getattr(lib, softmax_fwd)(*loss_args, s), "cham_score_softmax_fwd")
+        else:        # a pairwise ranking loss: the same outputs + the per-click record of its backward
+            check(getattr(lib, rankloss_fwd)(*loss_args, LOSS_FUNCTIONS.index(self.loss_function), self.bpr_max_reg, ptr(pl.ensure_rank_aux()), s),
+                  "cham_score_rankloss_fwd")
         if self.diversity_reg_factor > 0.0:      # + factor * p^T S p into nll, ahead of the loss record below (TRAIN and EVAL)
             sp, e = pl.ensure_diversity()
             check(lib.cham_diversity_fwd(ptr(pl.probs), ptr(d['ln_rows']), ptr(neg_ids), ptr(pl.mask), BT, N, ptr(rt.ace), rt.ace.stride(0),
@@ -1283,13 +1310,18 @@ class NARModuleModel:
         # (sum(mask): from the step-scalar record written by this step's forward, or by value)
         cosine = rt.cosine               # the cosine head: ds is all its backward needs of these two kernels (dcosq is their scratch output)
         if cosine:
-            softmax_bwd, diversity_bwd, S3, K3, w4, dS3 = 'cham_score_softmax_bwd', 'cham_diversity_bwd', pl.cosq, 4, rt.cos_w4, pl.dcosq
+            softmax_bwd, rankloss_bwd, diversity_bwd, S3, K3, w4, dS3 = ('cham_score_softmax_bwd', 'cham_score_rankloss_bwd', 'cham_diversity_bwd',
+                                                                         pl.cosq, 4, rt.cos_w4, pl.dcosq)
         else:
-            softmax_bwd, diversity_bwd, S3, K3, w4, dS3 = arm.softmax_bwd, arm.diversity_bwd, pl.S3, 32, p('Ws4'), pl.dS3
-        check(getattr(lib, softmax_bwd + ('_dev' if rt.dev_scalars else ''))(
-            ptr(S3), K3, ptr(w4), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
-            ptr(rt.scalars) if rt.dev_scalars else d['sum_mask'], ptr(pl.ds), ptr(dS3), self.novelty_reg_factor, ptr(neg_ids),
-            ptr(self._dev_state['pop_norm']), ptr(pl.logits), ptr(pl.nov_aux), s), "cham_score_softmax_bwd")
+            softmax_bwd, rankloss_bwd, diversity_bwd, S3, K3, w4, dS3 = arm.softmax_bwd, arm.rankloss_bwd, arm.diversity_bwd, pl.S3, 32, p('Ws4'), pl.dS3
+        loss_args = (ptr(S3), K3, ptr(w4), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
+                     ptr(rt.scalars) if rt.dev_scalars else d['sum_mask'], ptr(pl.ds), ptr(dS3), self.novelty_reg_factor, ptr(neg_ids),
+                     ptr(self._dev_state['pop_norm']), ptr(pl.logits), ptr(pl.nov_aux))
+        if self.loss_function == 'softmax':
+            check(getattr(lib, softmax_bwd + ('_dev' if rt.dev_scalars else ''))(*loss_args, s), "cham_score_softmax_bwd")
+        else:
+            check(getattr(lib, rankloss_bwd + ('_dev' if rt.dev_scalars else ''))(
+                *loss_args, LOSS_FUNCTIONS.index(self.loss_function), self.bpr_max_reg, ptr(pl.rank_aux), s), "cham_score_rankloss_bwd")
         if self.diversity_reg_factor > 0.0:      # ds += the diversity term's logit gradient, dS3 again from it
             check(getattr(lib, diversity_bwd)(
                 ptr(S3), K3, ptr(w4), ptr(pl.probs), ptr(pl.mask), BT, N, float(self.softmax_temperature),
@@ -1797,6 +1829,8 @@ class GraphedTrainStep:
             return "diversity regulariser (its two launches are not part of the captured step)"
         if rt.cosine:
             return "cosine ranking head (its launches are not part of the captured step)"
+        if m.loss_function != 'softmax':
+            return "loss_function %s (the captured step is the softmax loss's launch sequence)" % m.loss_function
         if self.key is not None and self.shape_key(d) != self.key:
             return "another batch shape than the captured one"
         if self.graph is None:      # capture needs a warm shape: buffers, workspaces, the step-scalar record and the kernels' dynamic-LDS

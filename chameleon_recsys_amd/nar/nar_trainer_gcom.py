@@ -98,6 +98,13 @@ def define_flags():
            "between the predicted session embedding and each candidate's contextual article embedding, then the same softmax with "
            "--softmax_temperature as the smoothing factor.  The cosine head has no matching_dense_layer variables; checkpoints of the two "
            "modes do not cross-load")
+    a('--loss_function', default='softmax', choices=['softmax', 'bpr', 'top1', 'bpr_max', 'top1_max'],
+      help="training objective over the scores of the positive and the sampled negatives: 'softmax' = the reference's sampled softmax + "
+           "negative log-likelihood (nar_model.py:639-667); 'bpr', 'top1' and their softmax-weighted '-max' forms = the pairwise ranking losses "
+           "of the reference's GRU4Rec baseline (benchmarks/gru4rec/gru4rec2.py), over scores / --softmax_temperature.  The ranked lists of "
+           "evaluation are defined as before; checkpoints cross-load between losses")
+    a('--bpr_max_reg', type=float, default=0.5, help="weight (>= 0) of the score regulariser of --loss_function bpr_max: lambda x the "
+      "softmax-weighted mean of the negatives' squared scores (0.5: the value of the reference's GRU4Rec run, bpr-max-0.5)")
     a('--gemm_dtype', default='f32', choices=['f32', 'f32_native', 'bf16'],
       help="f32: fp32 operands and fp32-grade error, wide GEMMs as six bf16-plane products on the bf16 matrix cores (caveats: an INFINITE "
            "operand yields NaN where fp32 yields +-inf - behind a tanh layer the native path saturates to a finite +-1 instead - and "
@@ -212,7 +219,8 @@ def nar_module_model_fn(features, labels, mode, params):
                            novelty_reg_factor=params['novelty_reg_factor'], diversity_reg_factor=params['diversity_reg_factor'],
                            internal_features_config=internal_features_config, eval_cold_start=params['eval_cold_start'],
                            rnn_cell=params.get('rnn_cell', 'ugrnn'), gemm_dtype=params.get('gemm_dtype', 'f32'),
-                           recommendations_ranking=params.get('recommendations_ranking', 'mlp'))
+                           recommendations_ranking=params.get('recommendations_ranking', 'mlp'),
+                           loss_function=params.get('loss_function', 'softmax'), bpr_max_reg=params.get('bpr_max_reg', 0.5))
     # under `python -m torch.distributed.run` (parallel.init_from_env): this rank's row shard of every batch, gradients summed over the ranks,
     # evaluation records reduced once per evaluate().  ONE wrapper per runtime, re-pointed at the model of this call.
     from .parallel import attach_data_parallel
@@ -258,6 +266,7 @@ def build_estimator(model_dir, content_article_embeddings_matrix, articles_metad
         'novelty_reg_factor': FLAGS.novelty_reg_factor, 'diversity_reg_factor': FLAGS.diversity_reg_factor,
         'eval_negative_sample_relevance': FLAGS.eval_negative_sample_relevance, 'eval_cold_start': FLAGS.eval_cold_start,
         'eval_beyond_accuracy_metrics': FLAGS.eval_beyond_accuracy_metrics,
+        'loss_function': FLAGS.loss_function, 'bpr_max_reg': FLAGS.bpr_max_reg,
         'session_features_config': session_features_config, 'articles_features_config': articles_features_config,
         'articles_metadata': articles_metadata, 'content_article_embeddings_matrix': content_article_embeddings_matrix})
 

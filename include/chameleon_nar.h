@@ -478,6 +478,40 @@ int cham_score_softmax_fwd(const float* S3, int K3, const float* w4, const float
 int cham_score_softmax_bwd(const float* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N,
                            float tau, float sum_mask, float* ds, float* dS3, float novelty_reg_factor, const int64_t* neg_ids,
                            const float* pop_norm, const float* logits, const float* nov_aux, void* stream);
+/* Pairwise ranking losses in place of the softmax / NLL pair above (--loss_function; csrc/rank_loss.hip).
+ * loss_kind: 1 bpr, 2 top1, 3 bpr_max, 4 top1_max.  With r_c = logit_c / tau, d_n = r_0 - r_n, s the logistic function and
+ * q = softmax(r_1..r_N) over the negatives alone (differentiated):
+ *   bpr -(1/N) sum log s(d_n);  top1 (1/N) sum [s(-d_n) + s(r_n^2)];  bpr_max -log(sum q_n s(d_n) + 1e-24) + bpr_max_reg sum q_n r_n^2;
+ *   top1_max sum q_n [s(-d_n) + s(r_n^2)].
+ * fwd writes logits, probs = softmax(logits / tau) over all 1 + N candidates (as cham_score_softmax_fwd does), nll[bt] = mask ? loss -
+ * novelty term : 0 and aux [BT,8], the per-click record its backward reads; bwd writes ds and dS3 in the contract of
+ * cham_score_softmax_bwd (its `probs` argument is not read; cham_diversity_bwd runs behind it unchanged).  Fixed summation order, no
+ * atomics.  Unknown loss_kind, N < 1, tau <= 0, a NULL pointer, sum_mask <= 0 (by-value form): -EINVAL, nothing launched. */
+int cham_score_rankloss_fwd(const float* S3, int K3, const float* w4, const float* b4, int BT, int N, float tau,
+                            const uint8_t* mask, float* logits, float* probs, float* nll, float novelty_reg_factor,
+                            const int64_t* neg_ids, const float* pop_norm, float* nov_aux, int loss_kind, float bpr_max_reg, float* aux,
+                            void* stream);
+int cham_score_rankloss_fwd_b16(const void* S3, int K3, const float* w4, const float* b4, int BT, int N, float tau,
+                                const uint8_t* mask, float* logits, float* probs, float* nll, float novelty_reg_factor,
+                                const int64_t* neg_ids, const float* pop_norm, float* nov_aux, int loss_kind, float bpr_max_reg, float* aux,
+                                void* stream);
+int cham_score_rankloss_bwd(const float* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N,
+                            float tau, float sum_mask, float* ds, float* dS3, float novelty_reg_factor, const int64_t* neg_ids,
+                            const float* pop_norm, const float* logits, const float* nov_aux, int loss_kind, float bpr_max_reg,
+                            const float* aux, void* stream);
+int cham_score_rankloss_bwd_b16(const void* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N,
+                                float tau, float sum_mask, float* ds, void* dS3, float novelty_reg_factor, const int64_t* neg_ids,
+                                const float* pop_norm, const float* logits, const float* nov_aux, int loss_kind, float bpr_max_reg,
+                                const float* aux, void* stream);
+/* ... with sum(mask) from the step-scalar record (see cham_score_softmax_bwd_dev) */
+int cham_score_rankloss_bwd_dev(const float* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N,
+                                float tau, const void* scalars, float* ds, float* dS3, float novelty_reg_factor, const int64_t* neg_ids,
+                                const float* pop_norm, const float* logits, const float* nov_aux, int loss_kind, float bpr_max_reg,
+                                const float* aux, void* stream);
+int cham_score_rankloss_bwd_b16_dev(const void* S3, int K3, const float* w4, const float* probs, const uint8_t* mask, int BT, int N,
+                                    float tau, const void* scalars, float* ds, void* dS3, float novelty_reg_factor, const int64_t* neg_ids,
+                                    const float* pop_norm, const float* logits, const float* nov_aux, int loss_kind, float bpr_max_reg,
+                                    const float* aux, void* stream);
 /* diversity_reg_factor > 0 adds the content-diversity regulariser of nar_model.py:551-636, 685-702 (commented out in the reference) to
  * the per-click loss: + factor * p^T S p, p = probs [BT,1+N] of the click, S_cc' = e^_c . e^_c' for candidates of DIFFERENT ids and 0 for
  * equal ids (the diagonal of the unique-id similarity matrix: zero padding of short negative lists included),
