@@ -159,6 +159,12 @@ _SIGNATURES = {
     "cham_acr_sigmoid_xent": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, c_int, P, P, c_size_t, P]),
     "cham_acr_relu": (c_int, [P, c_size_t, P]),
     "cham_acr_act_bwd": (c_int, [P, P, c_size_t, c_int, P]),
+    "cham_pairs_insert_cooc": (c_int, [P, c_int, c_int, c_int64, P, P, c_int64, P, P]),
+    "cham_pairs_insert_sr": (c_int, [P, c_int, c_int, c_int, c_int64, P, P, c_int64, P, P]),
+    "cham_pairs_rehash": (c_int, [P, P, c_int64, P, P, c_int64, P, P]),
+    "cham_pairs_export": (c_int, [P, P, c_int64, P, P, c_int64, P, P]),
+    "cham_baseline_scores": (c_int, [c_int, P, P, P, c_int, c_int, c_int64, P, P, c_int, c_int64, P, P, c_int64, P, P, P]),
+    "cham_baseline_rank": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

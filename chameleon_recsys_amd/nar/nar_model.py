@@ -1950,16 +1950,24 @@ class ItemsStateUpdaterHook:
       * under an active data-parallel wrapper (``model.dp``, nar/parallel.py) an EVAL pass covers this rank's session rows of every batch:
         the ranked lists stay on the device, the accuracy metrics come from the rank histogram (cham_eval_rank_hist), and end() reduces
         every record over the ranks ONCE (DataParallelNAR.reduce_eval_records) - every rank logs the same, global numbers.
-    Out of scope: the baseline recommenders (``eval_benchmark_classifiers`` must be empty), the
-    co-occurrence matrix (:1650), the metrics the reference defines but does not instantiate."""
+      * ``eval_benchmark_classifiers`` = names out of nar/baselines.BASELINE_NAMES ('pop_recent', 'cb', 'coocurrent', 'sr'): the reference's
+        order per batch - evaluate the baselines on the model's candidate rows (EVAL, :1607-1613), let them learn the batch (both modes,
+        :1627-1631), then the state update; their state (``eval_benchmarks_state``, a baselines.DeviceBaselines that outlives the hook) is
+        snapshotted and restored with the clicked-items state; end() merges 'hitrate_at_n_<name>' / 'mrr_at_n_<name>' into the results.
+    Out of scope: the ItemKNN / SessionKNN baselines and the reference's dict form of ``eval_benchmark_classifiers``,
+    the baselines' beyond-accuracy and cold-start records, the metrics the reference defines but does not instantiate."""
 
     def __init__(self, mode, model, eval_metrics_top_n, clicked_items_state, eval_sessions_metrics_log,
                  sessions_negative_items_log=None, sessions_chameleon_recommendations_log=None,
                  content_article_embeddings_matrix=None, articles_metadata=None, eval_negative_sample_relevance=None,
                  eval_benchmark_classifiers=[], eval_metrics_by_session_position=False, eval_cold_start=False,
-                 eval_metric_ops=None, eval_beyond_accuracy_metrics=False):
-        if eval_benchmark_classifiers:
+                 eval_metric_ops=None, eval_beyond_accuracy_metrics=False, eval_benchmarks_state=None):
+        from .baselines import BASELINE_NAMES
+        if eval_benchmark_classifiers and not (isinstance(eval_benchmark_classifiers, (list, tuple)) and
+                                               all(isinstance(x, str) and x in BASELINE_NAMES for x in eval_benchmark_classifiers)):
             raise NotImplementedError("baseline recommenders (nar/benchmarks) are out of scope: pass --disable_eval_benchmarks")
+        self.eval_benchmark_classifiers = tuple(eval_benchmark_classifiers or ())
+        self.baselines = eval_benchmarks_state if self.eval_benchmark_classifiers else None
         self.eval_cold_start = eval_cold_start
         self.eval_metrics_by_session_position = eval_metrics_by_session_position
         self.mode, self.model = mode, model
@@ -1975,6 +1983,18 @@ class ItemsStateUpdaterHook:
         self.eval_beyond_accuracy_metrics = eval_beyond_accuracy_metrics
 
     def begin(self):
+        if self.eval_benchmark_classifiers:
+            if self._data_parallel():
+                raise ValueError("eval_benchmarks: the baseline recommenders are not available in a data-parallel run")
+            if self.baselines is None:
+                from .baselines import DeviceBaselines
+                rt = self.model.rt
+                self.baselines = DeviceBaselines(self.eval_benchmark_classifiers, rt.n_items, rt.ace, device=rt.device)
+            if self.baselines.ace is None:
+                self.baselines.attach_ace(self.model.rt.ace)       # the matrix already resident in HBM
+            if self.mode == ModeKeys.EVAL:
+                self.baselines.save_state_checkpoint()
+                self.baselines.begin_evaluation(self.eval_metrics_top_n)
         if self.mode == ModeKeys.EVAL:
             from .metrics import HitRate, HitRateBySessionPosition, MRR, create_beyond_accuracy_metrics
             self.clicked_items_state.save_state_checkpoint()                    # nar_model.py:1415
@@ -2090,6 +2110,8 @@ class ItemsStateUpdaterHook:
         if self.eval_cold_start:                                               # nar_model.py:1621-1625, both modes
             self.update_items_cold_start_state(r['user_id'], clicked_items, next_item_labels, r['eval_batch_negative_items'],
                                                r['predicted_item_ids'])
+        if self.baselines is not None:
+            self._run_baselines()
         # state update, nar_model.py:1635-1649
         if getattr(self.clicked_items_state, 'is_device', False):     # straight from the batch tensors already in HBM
             d = self.model._d
@@ -2098,6 +2120,23 @@ class ItemsStateUpdaterHook:
         from .clicked_items_state import batch_clicks_for_state
         ids, ts = batch_clicks_for_state(clicked_items, last_item_label, clicked_timestamps)
         self.clicked_items_state.update_items_state(ids, ts)
+
+    def _run_baselines(self):
+        """The baselines' share of a step, on the step's stream, from the batch tensors already in HBM: evaluate BEFORE the batch is
+        learned (EVAL; nar_model.py:1607-1613), then learn it (both modes; :1627-1631).  No read-back."""
+        m, st = self.model, self.clicked_items_state
+        d = m._d
+        if self.mode == ModeKeys.EVAL:
+            recent_pop = None
+            if 'pop_recent' in self.eval_benchmark_classifiers:
+                if getattr(st, 'is_device', False):
+                    recent_pop = st.recent_pop
+                else:      # the counts behind the articles_recent_pop_norm this batch was fed
+                    recent_pop = torch.from_numpy(np.ascontiguousarray(st.get_articles_recent_pop(), dtype=np.int32)).to(m.rt.device)
+            self.baselines.evaluate(d['item_clicked'], d['label_next'], m._plan.neg_ids, recent_pop)
+            if recent_pop is not None and getattr(st, 'is_device', False):
+                st.note_consumed(d['aci'])         # recent_pop is read up to here: the state update waits for this
+        self.baselines.learn(d['aci'])
 
     def update_items_cold_start_state(self, users_ids, clicked_items, next_item_labels, eval_batch_negative_items, predicted_item_ids):
         """nar_model.py:1480-1494 (the benchmark recommenders' part, :1496-1501, is out of scope)."""
@@ -2157,5 +2196,11 @@ class ItemsStateUpdaterHook:
             self.eval_streaming_metrics_last['sessions_count'] = int(np.sum([x['batch_sessions_count'] for x in self.stats_logs]))
             if self.eval_cold_start:                                           # add_cold_start_stats, :1662-1666
                 self.eval_streaming_metrics_last['coldstart_chameleon'] = self.clicked_items_state.get_cold_start_state().get_statistics()
+            if self.baselines is not None:
+                self.eval_streaming_metrics_last.update(self.baselines.results(self.eval_metrics_top_n, self.eval_metrics_by_session_position))
             self.eval_sessions_metrics_log.append(self.eval_streaming_metrics_last)
             self.clicked_items_state.restore_state_checkpoint()
+        if self.baselines is not None:
+            self.baselines.check_tables()          # a dropped insert is an error (the growth rule makes it unreachable)
+            if self.mode == ModeKeys.EVAL:
+                self.baselines.restore_state_checkpoint()

@@ -7,8 +7,8 @@
 Same flag names / defaults (:37-91; the two ACR path flags are the ones ``main`` actually reads, :463-464), same
 feature configs (:99-218), ``nar_module_model_fn`` (:234-332), ``build_estimator`` (:335-386) and hourly
 train -> evaluate-next-hour loop (:511-525), metrics CSV (nar_utils.py:31-40).  Out of scope: GCS / ML-Engine
-plumbing (--use_local_cache_model_dir, --warmup_model_dir from GCS, TF_CONFIG trials) and the baseline recommenders
-(``--disable_eval_benchmarks`` is effectively always on).
+plumbing (--use_local_cache_model_dir, --warmup_model_dir from GCS, TF_CONFIG trials) and the ItemKNN / SessionKNN baselines.  The other
+four baseline recommenders run on the GPU when ``--eval_benchmarks`` names them (nar/baselines.py); without it none is evaluated.
 """
 import argparse
 import json
@@ -115,7 +115,24 @@ def define_flags():
            "create_eval_metrics list, nar_model.py:1709-1719; computed on the GPU); --eval_negative_sample_relevance weights the -RR pair")
     a('--clicked_items_state', default='host', choices=['host', 'device'], help="keep the recent-clicks state in host numpy (reference "
       "class) or in HBM (bit-identical, no host round trip per step)")
+    a('--eval_benchmarks', type=_list, default=[],
+      help="comma list of baseline recommenders evaluated on the model's candidate rows, their HitRate@n / MRR@n written beside the model's "
+           "(hitrate_at_n_<name>, mrr_at_n_<name>): pop_recent (most popular of the recent-clicks buffer), cb (content similarity to the "
+           "current item), coocurrent (session co-occurrence counts), sr (sequential rules, 'div' decay over 10 clicks).  Among equal scores "
+           "the smaller item id ranks first.  Empty (default): none; not combinable with --disable_eval_benchmarks")
+    a('--eval_benchmarks_max_pairs', type=int, default=1 << 25,
+      help="ceiling of the (item, item) entries each learned baseline (coocurrent, sr) may hold in device memory, 32 bytes per entry at "
+           "the table's load of 1/2; the run stops with an error beyond it")
     return ap
+
+
+def eval_benchmarks_from_flags(flags):
+    """Names of --eval_benchmarks in the reference's order; ValueError when --disable_eval_benchmarks contradicts them."""
+    from .baselines import parse_eval_benchmarks
+    names = parse_eval_benchmarks(getattr(flags, 'eval_benchmarks', []))
+    if names and getattr(flags, 'disable_eval_benchmarks', False):
+        raise ValueError("--eval_benchmarks %s contradicts --disable_eval_benchmarks: pass one of them" % ','.join(names))
+    return names
 
 
 FLAGS = define_flags().parse_args([])          # module-level defaults, replaced by main()
@@ -183,6 +200,7 @@ def l2_normalize_rows(x):
 
 # Global vars updated by the Estimator hook (nar_trainer_gcom.py:411-415)
 clicked_items_state = None
+eval_benchmarks_state = None           # nar/baselines.DeviceBaselines with --eval_benchmarks: lives across train / evaluate calls
 eval_sessions_metrics_log = []
 sessions_negative_items_log = None
 sessions_chameleon_recommendations_log = None
@@ -235,7 +253,8 @@ def nar_module_model_fn(features, labels, mode, params):
                                    content_article_embeddings_matrix=params['content_article_embeddings_matrix'],
                                    articles_metadata=params['articles_metadata'],
                                    eval_negative_sample_relevance=params['eval_negative_sample_relevance'],
-                                   eval_benchmark_classifiers=[],
+                                   eval_benchmark_classifiers=list(params.get('eval_benchmarks', ())),
+                                   eval_benchmarks_state=params.get('eval_benchmarks_state') or eval_benchmarks_state,
                                    eval_metrics_by_session_position=params['eval_metrics_by_session_position'],
                                    eval_cold_start=params['eval_cold_start'], eval_metric_ops=eval_metrics,
                                    eval_beyond_accuracy_metrics=params.get('eval_beyond_accuracy_metrics', False))]
@@ -267,6 +286,7 @@ def build_estimator(model_dir, content_article_embeddings_matrix, articles_metad
         'eval_negative_sample_relevance': FLAGS.eval_negative_sample_relevance, 'eval_cold_start': FLAGS.eval_cold_start,
         'eval_beyond_accuracy_metrics': FLAGS.eval_beyond_accuracy_metrics,
         'loss_function': FLAGS.loss_function, 'bpr_max_reg': FLAGS.bpr_max_reg,
+        'eval_benchmarks': eval_benchmarks_from_flags(FLAGS),
         'session_features_config': session_features_config, 'articles_features_config': articles_features_config,
         'articles_metadata': articles_metadata, 'content_article_embeddings_matrix': content_article_embeddings_matrix})
 
@@ -308,6 +328,7 @@ def train_and_evaluate_loop(flags, ace, articles_metadata, articles_features_con
 
 
 _DATA_PARALLEL_REFUSED_FLAGS = ('eval_cold_start', 'save_eval_sessions_negative_samples', 'save_eval_sessions_recommendations')
+_DATA_PARALLEL_REFUSED_LISTS = ('eval_benchmarks',)      # the baselines' tables and records are per process (follow-up)
 
 
 def _train_and_evaluate_loop(rank, world, ace, articles_metadata, articles_features_config, session_features_config, state_cls):
@@ -315,8 +336,13 @@ def _train_and_evaluate_loop(rank, world, ace, articles_metadata, articles_featu
     batch's integers) and trains / evaluates its own session rows of each batch.  Rank 0 alone writes the metrics CSV (every rank holds the
     same numbers) and prints the INFO lines; the Estimator writes the checkpoint on rank 0."""
     global clicked_items_state, eval_sessions_metrics_log, sessions_negative_items_log
-    global sessions_chameleon_recommendations_log, global_eval_hour_id
+    global sessions_chameleon_recommendations_log, global_eval_hour_id, eval_benchmarks_state
+    benchmarks = eval_benchmarks_from_flags(FLAGS)
     if world > 1:
+        for flag in _DATA_PARALLEL_REFUSED_LISTS:
+            if getattr(FLAGS, flag, None):
+                raise ValueError("--%s keeps its state and records per process: not supported under data parallelism (WORLD_SIZE=%d)"
+                                 % (flag, world))
         for flag in _DATA_PARALLEL_REFUSED_FLAGS:
             if getattr(FLAGS, flag, False):
                 raise ValueError("--%s needs every rank's ranked lists on one host: not supported under data parallelism (WORLD_SIZE=%d)"
@@ -334,6 +360,10 @@ def _train_and_evaluate_loop(rank, world, ace, articles_metadata, articles_featu
         state_cls = DeviceClickedItemsState
     clicked_items_state = state_cls(FLAGS.recent_clicks_buffer_hours, FLAGS.recent_clicks_buffer_max_size,
                                     FLAGS.recent_clicks_for_normalization, ace.shape[0])
+    eval_benchmarks_state = None
+    if benchmarks:
+        from .baselines import DeviceBaselines
+        eval_benchmarks_state = DeviceBaselines(benchmarks, ace.shape[0], None, max_pairs=FLAGS.eval_benchmarks_max_pairs)      # (ace: the runtime's, attached by the hook)
     model = build_estimator(FLAGS.model_dir, ace, articles_metadata, articles_features_config, session_features_config)
     train_files = resolve_files(FLAGS.train_set_path_regex)
     if FLAGS.train_files_from > FLAGS.train_files_up_to:

@@ -699,6 +699,41 @@ int cham_acr_sigmoid_xent(const float* logits, int ld, int B, int C, const int32
 int cham_acr_relu(float* x, size_t n, void* stream);
 int cham_acr_act_bwd(float* dy, const float* y, size_t n, int act, void* stream);
 
+/* --- Baseline recommenders of the evaluation (reference nar_module/nar/benchmarks; csrc/baselines.hip).
+ * PAIR TABLE: an open-addressing map (a, b) -> int64 weight in device memory: keys uint64 [cap] = (a << 32) | b with 0 = empty slot, vals
+ * int64 [cap], cap a power of two, meta int64 [2] = {inserts dropped because no slot was free, occupied slots}; the caller zeroes all
+ * three.  An insert claims a slot with a 64-bit compare-and-swap on the key and adds its weight with a 64-bit integer atomic add: the
+ * CONTENTS of the table do not depend on scheduling (slot positions may).  Every probe loop is bounded by cap.
+ * aci int64 [B, T1] session rows (zeros anywhere); the ids in [1, n_items) of a row, in order, are its session (T1 <= 1024, n_items <= 2^31):
+ *   insert_cooc   +1 for every DISTINCT ordered id pair (a, b) of two different positions of a session, once per session however often it
+ *                 repeats (an id clicked twice also yields (a, a) once) - scipy's M[rows, cols] += 1 over the session's permutations
+ *   insert_sr     += 2520 / (i - j) at (s_j, s_i) for 1 <= i - j <= max_dist (1..10): the 'div' decay 1 / (i - j) in units of 1 / 2520
+ *   rehash        every entry of (old_keys, old_vals) added into another table
+ *   export        the occupied slots in slot order of no meaning: n_out[0] (device) = their number, the first max_out of them written */
+int cham_pairs_insert_cooc(const int64_t* aci, int B, int T1, int64_t n_items, uint64_t* keys, int64_t* vals, int64_t cap, int64_t* meta,
+                           void* stream);
+int cham_pairs_insert_sr(const int64_t* aci, int B, int T1, int max_dist, int64_t n_items, uint64_t* keys, int64_t* vals, int64_t cap,
+                         int64_t* meta, void* stream);
+int cham_pairs_rehash(const uint64_t* old_keys, const int64_t* old_vals, int64_t old_cap, uint64_t* keys, int64_t* vals, int64_t cap,
+                      int64_t* meta, void* stream);
+int cham_pairs_export(const uint64_t* keys, const int64_t* vals, int64_t cap, uint64_t* keys_out, int64_t* vals_out, int64_t max_out,
+                      int64_t* n_out, void* stream);
+/* Scores of the 1 + N candidates {label_next[c]} + neg_ids[c, :] of each of the BT clicks (item_clicked, label_next [BT], neg_ids [BT, N]):
+ * score [BT, 1 + N] (int64 for kinds 0 and 2, fp32 for kind 1; 0 where not scored), scored uint8 [BT, 1 + N]; column 0 is the label; a
+ * click with label 0 is padding: nothing scored.  kind 0 'pop_recent': recent_pop int32 [n_items], scored iff the count is > 0.  kind 1 'cb':
+ * cosine of the ACE rows (fp32 [n_items, ace_ld], D columns used) of the clicked item and the candidate, a zero row normalised to zero;
+ * every candidate with an id in [0, n_items) is scored; fp32 accumulation in column order, independent of the candidate's column.  kind 2:
+ * the pair table's weight at (clicked item, candidate), scored iff the entry exists.  An id outside the table is never used as an index. */
+int cham_baseline_scores(int kind, const int64_t* item_clicked, const int64_t* label_next, const int64_t* neg_ids, int BT, int N,
+                         int64_t n_items, const int32_t* recent_pop, const float* ace, int D, int64_t ace_ld, const uint64_t* keys,
+                         const int64_t* vals, int64_t cap, void* score, uint8_t* scored, void* stream);
+/* Ranks each click's candidates by score (N + 1 <= 1024).  A candidate is live if it is scored and no earlier column holds the same id; it
+ * beats another if its score is larger, or equal with a smaller id.  label_rank int32 [BT] = number of live candidates that beat the label
+ * (max(N + 1, topn) when the label is not scored: a miss at every cut-off; -1 at padding), pred_ids int64 [BT, topn] = the live candidates
+ * in rank order, padded with 0. */
+int cham_baseline_rank(const void* score, int score_is_f32, const uint8_t* scored, const int64_t* label_next, const int64_t* neg_ids, int BT,
+                       int N, int topn, int32_t* label_rank, int64_t* pred_ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
