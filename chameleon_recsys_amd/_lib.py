@@ -165,6 +165,8 @@ _SIGNATURES = {
     "cham_pairs_export": (c_int, [P, P, c_int64, P, P, c_int64, P, P]),
     "cham_baseline_scores": (c_int, [c_int, P, P, P, c_int, c_int, c_int64, P, P, c_int, c_int64, P, P, c_int64, P, P, P]),
     "cham_baseline_rank": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P, P, P]),
+    "cham_vsknn_append": (c_int, [P, P, c_int, c_int, c_int64, c_int64, c_int, c_int, P, P, P, P, P]),
+    "cham_vsknn_scores": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

@@ -20,10 +20,9 @@
 //   k_baseline_rank one wave per click, ranking by counting: a candidate is LIVE if it is scored and no earlier column holds the same id
 //                   (the reference walks a ranking of unique items); rank = number of live candidates that beat it - larger score, or equal
 //                   score and smaller id (live ids are distinct: a strict total order, no ties left).
-#include "common.h"
+#include "baselines.h"
 
 #define BL_MAX_T1 1024
-#define BL_MAX_NC 1024
 #define BL_TILE 64
 #define BL_SR_SCALE 2520
 
@@ -139,11 +138,6 @@ __global__ __launch_bounds__(256) void k_pairs_export(const u64* __restrict__ ke
         keys_out[at] = k;
         vals_out[at] = vals[s];
     }
-}
-
-__device__ __forceinline__ int64_t cand_id(const int64_t* __restrict__ label_next, const int64_t* __restrict__ neg_ids, int64_t c, int col,
-                                           int N) {
-    return col == 0 ? label_next[c] : neg_ids[c * N + (col - 1)];
 }
 
 __global__ __launch_bounds__(256) void k_scores_int(int kind, const int64_t* __restrict__ item_clicked, const int64_t* __restrict__ label_next,
@@ -355,12 +349,16 @@ extern "C" int cham_baseline_scores(int kind, const int64_t* item_clicked, const
     return CHAM_OK;
 }
 
-extern "C" int cham_baseline_rank(const void* score, int score_is_f32, const uint8_t* scored, const int64_t* label_next,
+extern "C" int cham_baseline_rank(const void* score, int score_type, const uint8_t* scored, const int64_t* label_next,
                                   const int64_t* neg_ids, int BT, int N, int topn, int32_t* label_rank, int64_t* pred_ids, void* stream) {
-    if (!score || !scored || !label_next || !neg_ids || !label_rank || !pred_ids || BT < 0 || N < 1 || N + 1 > BL_MAX_NC || topn < 1)
+    if (!score || !scored || !label_next || !neg_ids || !label_rank || !pred_ids || BT < 0 || N < 1 || N + 1 > BL_MAX_NC || topn < 1 ||
+        score_type < 0 || score_type > 2)
         return -CHAM_ERR_ARG;
     if (BT == 0) return CHAM_OK;
-    if (score_is_f32)
+    if (score_type == 2)
+        hipLaunchKernelGGL(k_baseline_rank<double>, dim3((unsigned)BT), dim3(64), 0, (hipStream_t)stream, (const double*)score, scored,
+                           label_next, neg_ids, N, topn, label_rank, pred_ids);
+    else if (score_type == 1)
         hipLaunchKernelGGL(k_baseline_rank<float>, dim3((unsigned)BT), dim3(64), 0, (hipStream_t)stream, (const float*)score, scored,
                            label_next, neg_ids, N, topn, label_rank, pred_ids);
     else

@@ -1950,11 +1950,11 @@ class ItemsStateUpdaterHook:
       * under an active data-parallel wrapper (``model.dp``, nar/parallel.py) an EVAL pass covers this rank's session rows of every batch:
         the ranked lists stay on the device, the accuracy metrics come from the rank histogram (cham_eval_rank_hist), and end() reduces
         every record over the ranks ONCE (DataParallelNAR.reduce_eval_records) - every rank logs the same, global numbers.
-      * ``eval_benchmark_classifiers`` = names out of nar/baselines.BASELINE_NAMES ('pop_recent', 'cb', 'coocurrent', 'sr'): the reference's
+      * ``eval_benchmark_classifiers`` = names out of nar/baselines.BASELINE_NAMES ('pop_recent', 'cb', 'coocurrent', 'sr', 'v-sknn'): the reference's
         order per batch - evaluate the baselines on the model's candidate rows (EVAL, :1607-1613), let them learn the batch (both modes,
         :1627-1631), then the state update; their state (``eval_benchmarks_state``, a baselines.DeviceBaselines that outlives the hook) is
         snapshotted and restored with the clicked-items state; end() merges 'hitrate_at_n_<name>' / 'mrr_at_n_<name>' into the results.
-    Out of scope: the ItemKNN / SessionKNN baselines and the reference's dict form of ``eval_benchmark_classifiers``,
+    Out of scope: the ItemKNN ('item_knn') and undecayed SessionKNN ('sknn') baselines and the reference's dict form of ``eval_benchmark_classifiers``,
     the baselines' beyond-accuracy and cold-start records, the metrics the reference defines but does not instantiate."""
 
     def __init__(self, mode, model, eval_metrics_top_n, clicked_items_state, eval_sessions_metrics_log,
@@ -2136,7 +2136,10 @@ class ItemsStateUpdaterHook:
             self.baselines.evaluate(d['item_clicked'], d['label_next'], m._plan.neg_ids, recent_pop)
             if recent_pop is not None and getattr(st, 'is_device', False):
                 st.note_consumed(d['aci'])         # recent_pop is read up to here: the state update waits for this
-        self.baselines.learn(d['aci'])
+        session_ids = None
+        if 'v-sknn' in self.eval_benchmark_classifiers:      # the ring keeps the session ids: 8 bytes per row, host -> device
+            session_ids = torch.from_numpy(np.ascontiguousarray(np.asarray(m.session_id.eval()).reshape(-1), dtype=np.int64)).to(m.rt.device)
+        self.baselines.learn(d['aci'], session_ids)
 
     def update_items_cold_start_state(self, users_ids, clicked_items, next_item_labels, eval_batch_negative_items, predicted_item_ids):
         """nar_model.py:1480-1494 (the benchmark recommenders' part, :1496-1501, is out of scope)."""

@@ -7,8 +7,8 @@
 Same flag names / defaults (:37-91; the two ACR path flags are the ones ``main`` actually reads, :463-464), same
 feature configs (:99-218), ``nar_module_model_fn`` (:234-332), ``build_estimator`` (:335-386) and hourly
 train -> evaluate-next-hour loop (:511-525), metrics CSV (nar_utils.py:31-40).  Out of scope: GCS / ML-Engine
-plumbing (--use_local_cache_model_dir, --warmup_model_dir from GCS, TF_CONFIG trials) and the ItemKNN / SessionKNN baselines.  The other
-four baseline recommenders run on the GPU when ``--eval_benchmarks`` names them (nar/baselines.py); without it none is evaluated.
+plumbing (--use_local_cache_model_dir, --warmup_model_dir from GCS, TF_CONFIG trials) and the ItemKNN / undecayed SessionKNN baselines.  The other
+five baseline recommenders (V-SkNN among them) run on the GPU when ``--eval_benchmarks`` names them (nar/baselines.py); without it none is evaluated.
 """
 import argparse
 import json
@@ -118,8 +118,9 @@ def define_flags():
     a('--eval_benchmarks', type=_list, default=[],
       help="comma list of baseline recommenders evaluated on the model's candidate rows, their HitRate@n / MRR@n written beside the model's "
            "(hitrate_at_n_<name>, mrr_at_n_<name>): pop_recent (most popular of the recent-clicks buffer), cb (content similarity to the "
-           "current item), coocurrent (session co-occurrence counts), sr (sequential rules, 'div' decay over 10 clicks).  Among equal scores "
-           "the smaller item id ranks first.  Empty (default): none; not combinable with --disable_eval_benchmarks")
+           "current item), coocurrent (session co-occurrence counts), sr (sequential rules, 'div' decay over 10 clicks), v-sknn (session "
+           "kNN: cosine with the 'div' decay, last 3000 sessions, 1000 sampled, 500 neighbours; item_knn and sknn are not available).  "
+           "Among equal scores the smaller item id ranks first.  Empty (default): none; not combinable with --disable_eval_benchmarks")
     a('--eval_benchmarks_max_pairs', type=int, default=1 << 25,
       help="ceiling of the (item, item) entries each learned baseline (coocurrent, sr) may hold in device memory, 32 bytes per entry at "
            "the table's load of 1/2; the run stops with an error beyond it")

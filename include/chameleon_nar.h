@@ -727,12 +727,34 @@ int cham_pairs_export(const uint64_t* keys, const int64_t* vals, int64_t cap, ui
 int cham_baseline_scores(int kind, const int64_t* item_clicked, const int64_t* label_next, const int64_t* neg_ids, int BT, int N,
                          int64_t n_items, const int32_t* recent_pop, const float* ace, int D, int64_t ace_ld, const uint64_t* keys,
                          const int64_t* vals, int64_t cap, void* score, uint8_t* scored, void* stream);
-/* Ranks each click's candidates by score (N + 1 <= 1024).  A candidate is live if it is scored and no earlier column holds the same id; it
- * beats another if its score is larger, or equal with a smaller id.  label_rank int32 [BT] = number of live candidates that beat the label
- * (max(N + 1, topn) when the label is not scored: a miss at every cut-off; -1 at padding), pred_ids int64 [BT, topn] = the live candidates
- * in rank order, padded with 0. */
-int cham_baseline_rank(const void* score, int score_is_f32, const uint8_t* scored, const int64_t* label_next, const int64_t* neg_ids, int BT,
+/* Ranks each click's candidates by score (N + 1 <= 1024); score_type 0 = int64, 1 = fp32, 2 = fp64 scores.  A candidate is live if it is
+ * scored and no earlier column holds the same id; it beats another if its score is larger, or equal with a smaller id.  label_rank int32
+ * [BT] = number of live candidates that beat the label (max(N + 1, topn) when the label is not scored: a miss at every cut-off; -1 at
+ * padding), pred_ids int64 [BT, topn] = the live candidates in rank order, padded with 0. */
+int cham_baseline_rank(const void* score, int score_type, const uint8_t* scored, const int64_t* label_next, const int64_t* neg_ids, int BT,
                        int N, int topn, int32_t* label_rank, int64_t* pred_ids, void* stream);
+
+/* --- V-SkNN baseline (reference nar/benchmarks/session_knn.py: cosine, 'div' decay, 'recent' sampling; csrc/vsknn.hip).
+ * SESSION RING of S <= 4096 slots: items int32 [S, L] (a session's distinct ids in [1, n_items) in order of first occurrence, 0-padded;
+ * T1 <= L <= 65), lens int32 [S], ids int64 [S] (session ids), order int32 [S] (the slots by session id descending, slot ascending among
+ * equal ids); the caller zeroes items / lens / ids and starts order as 0..S-1.
+ *   append   row r of aci [B, T1] with session_ids [B] goes to slot (appended + r) mod S, `appended` = rows appended before this call
+ *            (counted by the caller); of more than S rows only the last S are written; a row without a valid id still takes its slot
+ *            (length 0); then order is rebuilt.
+ *   scores   per click (b, t) with item_clicked[b, t] != 0 (T <= 64, N + 1 <= 1024), over partial = item_clicked[b, 0..t]: a buffered
+ *            session s with m > 0 positions p <= t whose id it contains has decay = sum of 1 / (t - p + 1) over them (from p = t
+ *            downwards) and sim = decay / (sqrt(a) * sqrt(lens[s])), a = distinct values of partial; the session counts m times.  If the
+ *            copies of all sessions exceed `sample`, the sessions keep k = min(m, sample - copies kept so far) walking by session id
+ *            descending, else k = m.  Of the sessions with k > 0 and 0 < sim < 1, by (sim, session id) descending,
+ *            n = min(k, knn - copies kept so far).  score fp64 [B T, 1 + N] = sum over the sessions with n > 0 that hold the candidate of
+ *            n * sim (by session id descending; 0 where not scored), scored uint8 [B T, 1 + N].  fp64, round to nearest per operation,
+ *            no atomics: bit-reproducible.  sim_out fp64 / n_out int32 [B T, S] by SLOT (both or neither; sim of every session with
+ *            m > 0, else 0): for tests. */
+int cham_vsknn_append(const int64_t* aci, const int64_t* session_ids, int B, int T1, int64_t n_items, int64_t appended, int S, int L,
+                      int32_t* items, int32_t* lens, int64_t* ids, int32_t* order, void* stream);
+int cham_vsknn_scores(const int64_t* item_clicked, const int64_t* label_next, const int64_t* neg_ids, int B, int T, int N,
+                      const int32_t* items, const int32_t* lens, const int32_t* order, int S, int L, int sample, int knn, double* score,
+                      uint8_t* scored, double* sim_out, int32_t* n_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,11 @@
 #!/usr/bin/env python
-"""Per-batch cost of the baseline recommenders of the evaluation (nar/baselines.py, csrc/baselines.hip) at the G1 eval shape
-(B 256, T 20, 1 + N = 51 candidates, D 250, topn 10, 46 000 articles, G1-like session lengths), with pair tables learned from
---learn-batches batches first:
+"""Per-batch cost of the baseline recommenders of the evaluation (nar/baselines.py, csrc/baselines.hip, csrc/vsknn.hip) at the G1 eval
+shape (B 256, T 20, 1 + N = 51 candidates, D 250, topn 10, 46 000 articles, G1-like session lengths), with pair tables and the V-SkNN
+session ring (3000 sessions: full after 12 batches) learned from --learn-batches batches first:
 
-  * score + rank + histogram of the four baselines together (device events around DeviceBaselines.evaluate);
-  * learn (the co-occurrence and sequential-rules inserts, host growth rule included);
+  * score + rank + histogram of all baselines together, and of the four without 'v-sknn' (device events around
+    DeviceBaselines.evaluate); score + rank of each baseline alone;
+  * learn (the co-occurrence and sequential-rules inserts, host growth rule included, and the ring append), and the ring append alone;
   * the model's own evaluate_step on the same batches, from the same run - what the baselines are measured against;
   * the eager train_step without and with learn() behind it (learn also runs in TRAIN mode).
 
@@ -77,10 +78,15 @@ def main():
     dev_b = [train.upload_batch(f, l) for f, l in batches]
     # tables of a realistic size: sessions drawn like the batches' (fresh ids every pass, so the maps keep growing)
     rng = np.random.default_rng(0)
+    sid = {'next': 0}
+
+    def session_ids(rows):                       # ascending session ids, as a stream has them
+        sid['next'] += rows
+        return torch.arange(sid['next'] - rows, sid['next'], dtype=torch.int64, device=dev)
     for k in range(args.learn_batches):
         aci = dev_b[k % n_b]['aci']
         shift = torch.from_numpy(rng.integers(0, N_ITEMS - 1, size=(aci.shape[0], 1))).to(dev)
-        bl.learn(torch.where(aci != 0, (aci + shift) % (N_ITEMS - 1) + 1, aci))
+        bl.learn(torch.where(aci != 0, (aci + shift) % (N_ITEMS - 1) + 1, aci), session_ids(aci.shape[0]))
     bl.check_tables()
     entries = {n: t.counters()[1] for n, t in bl.tables.items()}
     caps = {n: t.cap for n, t in bl.tables.items()}
@@ -90,7 +96,7 @@ def main():
         train.feed_state(st, st)
         train.train_step(d)
         if learn:
-            bl.learn(d['aci'])
+            bl.learn(d['aci'], session_ids(B))
         st.update_from_device_batch(d['aci'], d['g_event_ts'])
     out = dict(shape=dict(B=B, T=T, NC=51, D=250, topn=10, n_items=N_ITEMS), length_dist=args.length_dist, valid_clicks=int(dev_b[0]['P']), table_entries=entries,
                table_slots=caps)
@@ -109,13 +115,21 @@ def main():
     def baselines(i):
         bl.evaluate(d['item_clicked'], d['label_next'], pl.neg_ids, st.recent_pop)
     out['baselines_evaluate_ms_median'], out['baselines_evaluate_ms_min'] = timed(baselines, args.iters)
+    bl.names = BASELINE_NAMES[:4]                # the four without the neighbour search
+    out['four_baselines_evaluate_ms_median'], out['four_baselines_evaluate_ms_min'] = timed(baselines, args.iters)
+    bl.names = BASELINE_NAMES
     for name in BASELINE_NAMES:
         med, mn = timed(lambda i: bl.score_and_rank(name, d['item_clicked'], d['label_next'], pl.neg_ids, st.recent_pop), args.iters)
         out['score_rank_%s_ms_median' % name] = med
-    out['learn_ms_median'], out['learn_ms_min'] = timed(lambda i: bl.learn(dev_b[i % n_b]['aci']), args.iters)
+    out['learn_ms_median'], out['learn_ms_min'] = timed(lambda i: bl.learn(dev_b[i % n_b]['aci'], session_ids(B)), args.iters)
+    out['learn_v-sknn_ms_median'], out['learn_v-sknn_ms_min'] = timed(lambda i: bl.ring.append(dev_b[i % n_b]['aci'], session_ids(B), N_ITEMS),
+                                                                      args.iters)
+    out['ring_sessions'] = min(bl.ring.appended, bl.ring.size)
     bl.check_tables()
     out['results'] = {k: float(v) for k, v in bl.results(10).items()}
     out['baselines_vs_evaluate_step'] = out['baselines_evaluate_ms_median'] / out['evaluate_step_ms_median']
+    out['four_baselines_vs_evaluate_step'] = out['four_baselines_evaluate_ms_median'] / out['evaluate_step_ms_median']
+    out['v-sknn_vs_evaluate_step'] = out['score_rank_v-sknn_ms_median'] / out['evaluate_step_ms_median']
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:
