@@ -20,6 +20,25 @@
 //   * Ws1's planes (written once per step by cham_split3) stream through LDS by LDS-DMA in half-stages of 64 columns x 64 k x 3 planes
 //     = 24 KB, two buffers; six plane products as in gemm_x3.hip / gemm_p3.hip.
 // Per half-stage and wave: 48 MFMAs, 24 ds_read_b128, 3 DMA requests, one barrier; every second half-stage the epilogue of a column tile.
+//
+// Schedule of column tile t (half-stages 2 t and 2 t + 1; NPL = planes per operand = DMA requests per half-stage: 3 | 2 (MODE 3) | 1 (MODE 2)).
+// vmcnt retires loads in the order of their issue, so "at most n outstanding" = everything older than the n youngest has landed:
+//   2 t     issue 16 Z2c row loads + 2 pred loads (tile t)      in flight: DMA(2 t + 1), the stores of tile t - 1 [older], the 18
+//           MFMAs on LDS buffer 0
+//           s_waitcnt vmcnt(18)                                 DMA(2 t + 1) and the stores of tile t - 1 are older than the 18: landed / gone
+//           barrier                                             (buffer 0 free, buffer 1 filled, every wave's sums of tile t - 1 in LDS)
+//           per-position column sums of tile t - 1 (LDS only: no global load), dpred / b2part out - they leave under the next products
+//           issue DMA(2 t + 2) -> buffer 0                      in flight: the 18, those stores, DMA(2 t + 2) [youngest]
+//   2 t + 1 MFMAs on LDS buffer 1                               (the 18 loads have had two half-stages of MFMAs and a barrier to land)
+//           s_waitcnt vmcnt(0)                                  DMA(2 t + 2) is the youngest request: only zero covers it - and the 18
+//           barrier                                             (buffer 1 free, buffer 0 filled, every wave done with the sums of tile t - 1)
+//           issue DMA(2 t + 3) -> buffer 1                      AHEAD of the epilogue's stores, not queued behind them
+//           epilogue of tile t from the registers loaded above: planes of dZ2 out, partial column sums AND the wave's pred values -> LDS
+//   after the last tile: barrier, its column sums.
+// Two barriers per tile, as before.  Nothing is loaded between a wait and the use it covers, so no global-memory round trip is exposed in
+// the loop; the last tile issues no DMA.
+// The count 18 does not depend on the MODE (bf16: 16 dword loads + 2 pred loads).  Requests a compiler may add (none at present: no
+// instance uses scratch) are younger than the DMA they would be counted against and make the wait stricter, never weaker.
 #include "gemm_shared.h"
 #include <type_traits>
 
@@ -27,8 +46,9 @@
 #define DMF_COLS (32 * DMF_NT)                // columns per column tile
 #define DMF_PLANE (DMF_COLS * 128)            // one plane of a half-stage: DMF_COLS slots x 64 k x 2 B
 #define DMF_HALF (3 * DMF_PLANE)              // one half-stage: three planes
-#define DMF_RED_OFF (2 * DMF_HALF)            // [8 waves][2 slots][2 quantities][DMF_COLS columns] fp32
-#define DMF_RED_BYTES (8 * 4 * DMF_COLS * 4)
+#define DMF_RED_OFF (2 * DMF_HALF)            // [8 waves]{[2 slots][2 quantities][DMF_COLS columns], [2 slots][DMF_COLS columns] of pred} fp32
+#define DMF_RED_WAVE (6 * DMF_COLS)           // floats per wave
+#define DMF_RED_BYTES (8 * DMF_RED_WAVE * 4)
 
 static_assert(DMF_NT == 2, "the epilogue packs exactly two tiles' columns per lane");
 
@@ -53,6 +73,36 @@ __device__ __forceinline__ void dmf_dma_one(unsigned lds, unsigned voff, const u
         "s_mov_b32 m0, %0"
         : "=&s"(keep) : "s"(lds), "v"(voff), "s"(r) : "memory");
 }
+
+// tanh' = 1 - z^2 of the epilogue with its rounding SPELLED OUT: one rounding (fma) or two (product, then difference).  Left to the
+// compiler's contraction the choice fell differently from instance to instance and, in MODE 0 / 1, from row to row, and it moves with
+// any change of the code around it - the last bit of dZ2 and of b2part with it.  dmf_tanh_fused() records what each instance has computed
+// since it was first built; the results are held to those bits (tests/test_dm_fused_schedule_gpu.py).
+template <bool FUSED>
+__device__ __forceinline__ float dmf_one_minus_sq(float z) {
+    if constexpr (FUSED) {
+        return __builtin_fmaf(-z, z, 1.f);
+    } else {
+#pragma clang fp contract(off)
+        const float q = z * z;
+        return 1.f - q;
+    }
+}
+// MODE 3: every row fused; MODE 2 (bf16): none; MODE 0 / 1: the lane's rows e >= 8
+__host__ __device__ constexpr bool dmf_tanh_fused(int mode, int e) { return mode == 3 || (mode != 2 && e >= 8); }
+// ... and, MODE 0, the three bf16 planes of o = x * t: the middle plane's residual o - h comes from the ROUNDED product, or (rows e < 7) from
+// the unrounded one in one fma - the same history
+template <bool RESID_FUSED>
+__device__ __forceinline__ void dmf_split3_prod(float x, float t, float& o, __bf16& h, __bf16& m, __bf16& l) {
+#pragma clang fp contract(off)
+    o = x * t;
+    h = (__bf16)o;
+    float r = RESID_FUSED ? __builtin_fmaf(x, t, -(float)h) : o - (float)h;
+    m = (__bf16)r;
+    r -= (float)m;
+    l = (__bf16)r;
+}
+__host__ __device__ constexpr bool dmf_resid_fused(int mode, int e) { return mode == 0 && e < 7; }
 
 // MODE 0: three bf16 planes out (csrc/gemm_p3.hip).  MODE 1: the output as two fp16 planes x a power-of-two scale (csrc/gemm_h2.hip); the
 // kernel's own products (dS1 x Ws1, K = 128: 12 % of its time) stay six bf16 plane products - its time is the 1 GB of Z2 in and the planes
@@ -237,44 +287,106 @@ __global__ __launch_bounds__(512) void k_dm_mulpred_fused(DmfParams p) {
             }
         }
     };
-    for (int h = 0; h < nhalf; ++h) {
-        if (h & 1) mfma_half(std::integral_constant<int, 1>{});
-        else mfma_half(std::integral_constant<int, 0>{});
-        __builtin_amdgcn_sched_barrier(0);
-        // this wave's requests for half-stage h + 1 (issued a half-stage ago) have landed; nothing else of its is in flight except
-        // the previous tile's stores
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (h & 1) {
-            // ---- epilogue of column tile h / 2: lane n holds columns n0 + 2 n, n0 + 2 n + 1 of its 16 rows
-            const int col = (h >> 1) * DMF_COLS + DMF_NT * l31;
-            float2 pra = make_float2(0.f, 0.f), prb = pra;
-            if (pa < npos) pra = *reinterpret_cast<const float2*>(p.pred + (size_t)(pos0 + pa) * C + col);
-            if (pa + 1 < npos) prb = *reinterpret_cast<const float2*>(p.pred + (size_t)(pos0 + pa + 1) * C + col);
-            float2 sa = make_float2(0.f, 0.f), sb = sa, ca = sa, cb = sa;
-            typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-            u32x2_t zz[16];
+    // ---- the operands of a column tile's epilogue: this lane's 16 rows of Z2c (two consecutive columns each) and the pred rows of the wave's
+    // two positions.  ALWAYS 18 requests, in this order, without a branch: the counted wait below depends on it.  Rows beyond the valid
+    // ones and positions beyond npos read zeros through the descriptors.
+    const __amdgpu_buffer_rsrc_t pw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.pred + (size_t)pos0 * C), 0,
+                                                                        (unsigned)((size_t)npos * C * 4), 0x00020000);
+    typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+    typedef std::conditional_t<B16, unsigned, u32x2_t> dmf_zraw;         // B16: two bf16 in one dword
+    dmf_zraw zz[16];
+    u32x2_t pz[2];
+    auto load_tile = [&](int t) {
+        const unsigned col = (unsigned)(t * DMF_COLS + DMF_NT * l31);
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {      // all sixteen row loads in flight at once (rows beyond the valid ones: zeros)
-                const unsigned r = (unsigned)(wr0 + (e & 3) + 8 * (e >> 2) + 4 * hh);
-                if constexpr (B16) {            // two bf16 -> two fp32 bit patterns (exact)
-                    const unsigned u = __builtin_amdgcn_raw_buffer_load_b32(zw, (r * (unsigned)C + (unsigned)col) * 2u, 0, 0);
-                    zz[e].x = u << 16; zz[e].y = u & 0xFFFF0000u;
-                } else {
-                    zz[e] = __builtin_amdgcn_raw_buffer_load_b64(zw, (r * (unsigned)C + (unsigned)col) * 4u, 0, 0);
-                }
+        for (int e = 0; e < 16; ++e) {          // all sixteen row loads in flight at once
+            const unsigned r = (unsigned)(wr0 + (e & 3) + 8 * (e >> 2) + 4 * hh);
+            if constexpr (B16) zz[e] = __builtin_amdgcn_raw_buffer_load_b32(zw, (r * (unsigned)C + col) * 2u, 0, 0);
+            else zz[e] = __builtin_amdgcn_raw_buffer_load_b64(zw, (r * (unsigned)C + col) * 4u, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) pz[i] = __builtin_amdgcn_raw_buffer_load_b64(pw, ((unsigned)(pa + i) * (unsigned)C + col) * 4u, 0, 0);
+    };
+    auto sync_stage = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    };
+    // ---- per-position column sums of column tile t (after the barrier behind its epilogue): thread (position, column) adds the waves in
+    // ascending order
+    auto col_sums = [&](int t) {
+        const float* redw = reinterpret_cast<const float*>(dmf_smem + DMF_RED_OFF);
+        for (int idx = threadIdx.x; idx < npos * DMF_COLS; idx += 512) {
+            const int pl = idx / DMF_COLS, c = idx % DMF_COLS;
+            float s = 0.f, cs = 0.f;
+            const int w_lo = (pl * NC) >> 5, w_hi = min(7, ((pl + 1) * NC - 1) >> 5);
+            for (int w = w_lo; w <= w_hi; ++w) {
+                const int slot = (pl == (32 * w) / NC) ? 0 : 1;
+                s += redw[(size_t)w * DMF_RED_WAVE + slot * (2 * DMF_COLS) + c];
+                cs += redw[(size_t)w * DMF_RED_WAVE + slot * (2 * DMF_COLS) + DMF_COLS + c];
             }
+            const int colg = t * DMF_COLS + c;
+            // pred[pos0 + pl, colg]: every wave of the position holds the same bits; the first one's
+            const float pr = redw[(size_t)w_lo * DMF_RED_WAVE + (4 + ((pl == (32 * w_lo) / NC) ? 0 : 1)) * DMF_COLS + c];
+            p.dpred[(size_t)(pos0 + pl) * C + colg] = s * dmf_one_minus_sq<true>(pr);
+            if (p.b2part) p.b2part[(size_t)(pos0 + pl) * C + colg] = cs;
+        }
+    };
+    for (int t = 0; t < ntiles; ++t) {
+        // ---- half-stage 2 t: the tile's loads go out first and land under its 2 x (48 | 24 | 8) MFMAs and the barrier between them
+        load_tile(t);
+        mfma_half(std::integral_constant<int, 0>{});
+        __builtin_amdgcn_sched_barrier(0);
+        // this wave's NPL requests for half-stage 2 t + 1 (issued a half-stage ago) and the previous tile's stores are OLDER than the 18
+        // loads above and the vector-memory counter retires loads in order: at most 18 outstanding = the requests have landed (every
+        // MODE issues the same 18, so the count does not depend on NPL)
+        asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+        sync_stage();                           // every wave: done reading buffer 0, its requests for 2 t + 1 landed, its sums of tile t - 1 are in LDS
+        if (t > 0) col_sums(t - 1);             // (its stores leave under the products; `red` is written again behind the NEXT barrier)
+        // (requested behind the loads: were it in front of them, the compiler's wait for the loads would wait for it too)
+        if (2 * t + 2 < nhalf) dma_half(2 * t + 2);
+        // ---- half-stage 2 t + 1
+        mfma_half(std::integral_constant<int, 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        // the requests for half-stage 2 t + 2 are the YOUNGEST in flight: only zero covers them - and the tile's loads, used next
+        // (the loaded registers pass through the statement: the compiler places its own wait for them HERE, where everything has to have
+        // landed anyway, and not behind the request below, which it would then wait for as well)
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(zz[0]), "+v"(zz[1]), "+v"(zz[2]), "+v"(zz[3]), "+v"(zz[4]), "+v"(zz[5]), "+v"(zz[6]), "+v"(zz[7]), "+v"(zz[8]), "+v"(zz[9]),
+                       "+v"(zz[10]), "+v"(zz[11]), "+v"(zz[12]), "+v"(zz[13]), "+v"(zz[14]), "+v"(zz[15]), "+v"(pz[0]), "+v"(pz[1])
+                     :: "memory");
+        sync_stage();                           // every wave: done reading buffer 1, its requests for 2 t + 2 landed, done with the sums of tile t - 1
+        // buffer 1 is free: its next half-stage is requested BEFORE the epilogue's stores, not queued behind them
+        if (2 * t + 3 < nhalf) dma_half(2 * t + 3);
+        {
+            // ---- epilogue of column tile t: lane n holds columns n0 + 2 n, n0 + 2 n + 1 of its 16 rows
+            const int col = t * DMF_COLS + DMF_NT * l31;
+            const float2 pra = make_float2(__uint_as_float(pz[0].x), __uint_as_float(pz[0].y));
+            const float2 prb = make_float2(__uint_as_float(pz[1].x), __uint_as_float(pz[1].y));
+            float2 sa = make_float2(0.f, 0.f), sb = sa, ca = sa, cb = sa;
+            // MODE 1 (96 VGPRs of A fragments AND the two-plane epilogue) has no room for the sixteen per-row offsets of the blocked layout
+            // that the compiler would keep across the tile loop (they went to scratch): opaque per tile, they are recomputed
+            unsigned rin_t = rin;
+            if constexpr (MODE == 1) asm volatile("" : "+s"(rin_t));
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int rr = (e & 3) + 8 * (e >> 2) + 4 * hh;           // row relative to the wave's first row
                 const unsigned r = (unsigned)(wr0 + rr);
-                const float2 z = make_float2(__uint_as_float(zz[e].x), __uint_as_float(zz[e].y));
+                float2 z;
+                if constexpr (B16) z = make_float2(__uint_as_float(zz[e] << 16), __uint_as_float(zz[e] & 0xFFFF0000u));   // two bf16 -> fp32 (exact)
+                else z = make_float2(__uint_as_float(zz[e].x), __uint_as_float(zz[e].y));
                 const bool second = rr >= bnd;
                 const float2 pr = second ? prb : pra;
                 float2 g = make_float2(acc[0][e], acc[1][e]);      // (zero on rows beyond the valid ones: their dS1 rows read as zeros)
                 if constexpr (F16P) { g.x = (g.x * ginv_a) * ginv_w; g.y = (g.y * ginv_a) * ginv_w; }  // back to true units (powers of two)
                 if constexpr (B16) { g.x = (float)(__bf16)g.x; g.y = (float)(__bf16)g.y; }      // dM as the unfused pair stores it
                 float2 o;
-                o.x = g.x * pr.x * (1.f - z.x * z.x); o.y = g.y * pr.y * (1.f - z.y * z.y);
+                const bool fz = dmf_tanh_fused(MODE, e);                   // (a constant once the loop is unrolled)
+                const float2 tz = fz ? make_float2(dmf_one_minus_sq<true>(z.x), dmf_one_minus_sq<true>(z.y))
+                                     : make_float2(dmf_one_minus_sq<false>(z.x), dmf_one_minus_sq<false>(z.y));
+                const float2 gp = make_float2(g.x * pr.x, g.y * pr.y);
+                o.x = gp.x * tz.x; o.y = gp.y * tz.y;
                 if constexpr (B16) {
                     typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
                     bf16x2_t ph; ph[0] = (__bf16)o.x; ph[1] = (__bf16)o.y;
@@ -287,7 +399,7 @@ __global__ __launch_bounds__(512) void k_dm_mulpred_fused(DmfParams p) {
                     const unsigned pl = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
                     unsigned oo = (r * (unsigned)C + (unsigned)col) * 2u;
                     if (oblk) {
-                        const unsigned lr = rin + r;              // row counted from the first row of the window's first tile
+                        const unsigned lr = rin_t + r;             // row counted from the first row of the window's first tile
                         oo = (int)r < rows_valid ? (lr >> 8) * tile_bytes + ((unsigned)col >> 5) * (unsigned)(H2B_BLOCK * 2) + (lr & 255u) * 64u + ((unsigned)col & 31u) * 2u
                                                  : 0x80000000u;
                     }
@@ -297,8 +409,11 @@ __global__ __launch_bounds__(512) void k_dm_mulpred_fused(DmfParams p) {
                     typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
                     bf16x2_t ph, pm, pl;
                     __bf16 a, b, c;
-                    split3(o.x, a, b, c); ph[0] = a; pm[0] = b; pl[0] = c;
-                    split3(o.y, a, b, c); ph[1] = a; pm[1] = b; pl[1] = c;
+                    const bool fr = dmf_resid_fused(MODE, e);              // (a constant once the loop is unrolled)
+                    if (fr) dmf_split3_prod<true>(gp.x, tz.x, o.x, a, b, c); else dmf_split3_prod<false>(gp.x, tz.x, o.x, a, b, c);
+                    ph[0] = a; pm[0] = b; pl[0] = c;
+                    if (fr) dmf_split3_prod<true>(gp.y, tz.y, o.y, a, b, c); else dmf_split3_prod<false>(gp.y, tz.y, o.y, a, b, c);
+                    ph[1] = a; pm[1] = b; pl[1] = c;
                     const unsigned oo = (r * (unsigned)C + (unsigned)col) * 2u;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ph), ow[0], oo, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pm), ow[1], oo, 0, 0);
@@ -310,7 +425,9 @@ __global__ __launch_bounds__(512) void k_dm_mulpred_fused(DmfParams p) {
                 acc[0][e] = 0.f; acc[1][e] = 0.f;
             }
             // the other half-wave holds the other 16 rows of the same columns: lower half + upper half, in that order
-            float* red = reinterpret_cast<float*>(dmf_smem + DMF_RED_OFF) + (size_t)wave * (4 * DMF_COLS);       // [slot 2][quantity 2][DMF_COLS]
+            // (next to the sums: the pred values of the lane's two columns for the wave's two positions - col_sums() takes
+            // them from here, not from global memory)
+            float* red = reinterpret_cast<float*>(dmf_smem + DMF_RED_OFF) + (size_t)wave * DMF_RED_WAVE;  // [slot 2][quantity 2][DMF_COLS], [slot 2][DMF_COLS]
             float2 q[4] = {sa, ca, sb, cb};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -318,35 +435,14 @@ __global__ __launch_bounds__(512) void k_dm_mulpred_fused(DmfParams p) {
                 o.x = __shfl_xor(q[i].x, 32, 64); o.y = __shfl_xor(q[i].y, 32, 64);
                 if (hh == 0) *reinterpret_cast<float2*>(red + i * DMF_COLS + DMF_NT * l31) = make_float2(q[i].x + o.x, q[i].y + o.y);
             }
-        }
-        // every wave: done reading buffer h & 1, its requests for h + 1 landed (and, on odd h, its partial sums are in LDS)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-        if (h & 1) {
-            // ---- per-position column sums of this column tile: thread (position, column) adds the waves in ascending order
-            const float* redw = reinterpret_cast<const float*>(dmf_smem + DMF_RED_OFF);
-            for (int idx = threadIdx.x; idx < npos * DMF_COLS; idx += 512) {
-                const int pl = idx / DMF_COLS, c = idx % DMF_COLS;
-                float s = 0.f, cs = 0.f;
-                const int w_lo = (pl * NC) >> 5, w_hi = min(7, ((pl + 1) * NC - 1) >> 5);
-                for (int w = w_lo; w <= w_hi; ++w) {
-                    const int slot = (pl == (32 * w) / NC) ? 0 : 1;
-                    s += redw[(size_t)w * (4 * DMF_COLS) + slot * (2 * DMF_COLS) + c];
-                    cs += redw[(size_t)w * (4 * DMF_COLS) + slot * (2 * DMF_COLS) + DMF_COLS + c];
-                }
-                const int colg = (h >> 1) * DMF_COLS + c;
-                const float pr = p.pred[(size_t)(pos0 + pl) * C + colg];
-                p.dpred[(size_t)(pos0 + pl) * C + colg] = s * (1.f - pr * pr);
-                if (p.b2part) p.b2part[(size_t)(pos0 + pl) * C + colg] = cs;
+            if (hh == 0) {
+                *reinterpret_cast<float2*>(red + 4 * DMF_COLS + DMF_NT * l31) = pra;
+                *reinterpret_cast<float2*>(red + 5 * DMF_COLS + DMF_NT * l31) = prb;
             }
-            // (the next epilogue writes `red` again only after the next two barriers)
         }
-        // (requested only now: the loads of the block above are visible to the compiler, whose wait for them would also wait for
-        // requests issued before them)
-        if (h + 2 < nhalf) dma_half(h + 2);
     }
+    sync_stage();
+    col_sums(ntiles - 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
