@@ -733,7 +733,11 @@ __global__ __launch_bounds__(256) void k_split2h(const float* __restrict__ X, in
         const int r = (int)(i / Cc), c = (int)(i % Cc);
         const float x = X[(size_t)r * ld + c];
         _Float16 h, l;
-        split2h(x * s, h, l);
+        // the product as a value of its own: left to the compiler, fp16(x * s) became ONE v_fma_mixlo_f16 with a +0 addend, and x = -0 stored
+        // h = +0, l = -0 where every other producer (v_mul_f32, then v_cvt_f16_f32) stores h = -0, l = +0 (tests/test_plane_producers_gpu.py)
+        float xs = x * s;
+        asm volatile("" : "+v"(xs));
+        split2h(xs, h, l);
         const unsigned short hb = h2_keep_sign(h, x);
         if (dst) { _Float16* d = dst + (size_t)r * ldd + c; *reinterpret_cast<unsigned short*>(d) = hb; d[ps] = l; }
         if (dstT) { _Float16* d = dstT + (size_t)c * lddT + r; *reinterpret_cast<unsigned short*>(d) = hb; d[psT] = l; }
