@@ -167,6 +167,11 @@ _SIGNATURES = {
     "cham_baseline_rank": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P, P, P]),
     "cham_vsknn_append": (c_int, [P, P, c_int, c_int, c_int64, c_int64, c_int, c_int, P, P, P, P, P]),
     "cham_vsknn_scores": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "cham_predict_candidates_workspace_bytes": (c_size_t, [c_int64]),
+    "cham_predict_candidates": (c_int, [P, c_int, c_int64, P, c_int64, P, P, c_size_t, P]),
+    "cham_predict_fill_chunk": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "cham_predict_topn_merge": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, c_int, c_float, P, P, P, P]),
+    "cham_predict_topn_finish": (c_int, [P, P, c_int, c_int, c_float, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

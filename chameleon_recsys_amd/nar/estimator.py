@@ -33,17 +33,20 @@ class RunConfig:
 
 class EstimatorSpec:
     def __init__(self, mode, loss=None, train_op=None, eval_metric_ops=None, training_chief_hooks=None, training_hooks=None,
-                 evaluation_hooks=None, predictions=None):
+                 evaluation_hooks=None, predictions=None, prediction_hooks=None):
         self.mode, self.loss, self.train_op = mode, loss, train_op
         self.eval_metric_ops = eval_metric_ops or {}
         self.training_chief_hooks = list(training_chief_hooks or [])
         self.training_hooks = list(training_hooks or [])
         self.evaluation_hooks = list(evaluation_hooks or [])
+        self.prediction_hooks = list(prediction_hooks or [])
         self.predictions = predictions
         if mode == ModeKeys.TRAIN and (loss is None or train_op is None):
             raise ValueError("Missing loss / train_op for ModeKeys.TRAIN")
         if mode == ModeKeys.EVAL and loss is None:
             raise ValueError("Missing loss for ModeKeys.EVAL")
+        if mode == ModeKeys.PREDICT and predictions is None:
+            raise ValueError("Missing predictions for ModeKeys.PREDICT")
 
 
 class SessionRunArgs:
@@ -232,7 +235,10 @@ class Estimator:
 
     # ---- the session.run loop
     def _call_model_fn(self, input_fn, mode):
-        features, labels = input_fn()
+        out = input_fn()
+        features, labels = out if isinstance(out, tuple) and len(out) == 2 else (out, None)
+        if mode == ModeKeys.PREDICT:
+            labels = None                     # labels from input_fn, if present, are ignored
         had_rt = self._store.get('runtime') is not None
         with nar_model.variable_store(self._store):
             spec = self._model_fn(features, labels, mode, self.params)
@@ -323,3 +329,35 @@ class Estimator:
         out['loss'] = loss_sum / max(1, n)
         out['global_step'] = self.global_step
         return out
+
+    def predict(self, input_fn, hooks=None, predict_top_n=10, candidates=None):
+        """Top-n next articles for the sessions ``input_fn`` yields (labels, if it yields any, are ignored): a generator of one dict per
+        session - ``session_id``, ``item_ids`` int64 [n], ``scores`` float32 [n], ``probs`` float32 [n] (NARModuleModel.predict_step).  Calls
+        ``model_fn`` in ModeKeys.PREDICT; the spec's ``predictions`` is the model, its ``prediction_hooks`` feed the clicked-items state.
+        ``candidates``: item ids that replace the default candidate set (the distinct ids of the recent-clicks buffer)."""
+        from .predict import check_top_n
+        n = check_top_n(predict_top_n)        # (raised here, not at the first next())
+        rt = self._store.get('runtime')
+        if rt is not None and getattr(rt, 'dp_active', False):
+            raise ValueError("Estimator.predict is not available in a data-parallel run")
+        return self._predict(input_fn, hooks, n, candidates)
+
+    def _predict(self, input_fn, hooks, n, candidates):
+        features, _, spec = self._call_model_fn(input_fn, ModeKeys.PREDICT)
+        ds = features.dataset
+        model = spec.predictions
+        all_hooks = list(spec.prediction_hooks) + list(hooks or [])
+        ctx = SessionRunContext(model)
+        for h in all_hooks:
+            h.begin()
+        try:
+            while ds.advance():
+                out = self._run_hooks_step(all_hooks, ctx, lambda: model.predict_step(None, n, candidates))
+                sids = np.asarray(features['session_id']).reshape(-1)
+                for b in range(out['item_ids'].shape[0]):
+                    yield {'session_id': sids[b], 'item_ids': out['item_ids'][b], 'scores': out['scores'][b], 'probs': out['probs'][b]}
+        finally:
+            for h in all_hooks:
+                h.end(None)
+            ds.close()
+        self._check_device_health(collective=False)

@@ -1661,6 +1661,31 @@ class NARModuleModel:
         self._eval_iter += 1
         return self.total_loss
 
+    # ------------------------------------------------------------------ top-n prediction for open sessions (nar/predict.py, csrc/predict.hip)
+    def upload_predict_batch(self, features):
+        """Features batch as input_fn yields it (labels are not needed) -> the device batch predict_step takes."""
+        from . import predict
+        return predict.upload_predict_batch(self, features)
+
+    def predict_step(self, device_batch=None, topn=10, candidates=None, chunk_candidates=None):
+        """PREDICT-mode ``session.run``: for every session of the batch the `topn` (1..64) candidates most likely to be clicked next after its
+        last click.  Candidates: `candidates` (item ids in [1, n_items); de-duplicated and sorted) or, by default, the
+        distinct ids of the fed recent-clicks buffer; a session's own clicks are excluded.  The score of a candidate is the logit the EVAL
+        forward gives it as a negative sample of the session's last click; probs = softmax(score / softmax_temperature) over the session's
+        non-excluded candidates; order: score descending, smaller id first among equal scores; lists shorter than topn are padded with id 0,
+        score -inf, prob 0 (a session without a click: all padding).  The candidates are scored in chunks of `chunk_candidates` (default: as
+        many as keep the chunk's P_last (1 + Nc) candidate rows within those of the model's training plan).  Returns numpy arrays
+        item_ids int64 / scores / probs float32 [B, topn] and K (candidates), Nc, chunks, P_last, candidates (the ids, ascending).
+        Leaves the weights, the clicked-items state, global_step, the sampler keys and every evaluation record as they are."""
+        from . import predict
+        predict.check_top_n(topn)
+        d = device_batch if device_batch is not None else self.upload_predict_batch(self.inputs)
+        depth = _roctx.depth()
+        try:
+            return predict.predict_step(self, d, topn, candidates, chunk_candidates)
+        finally:
+            _roctx.unwind(depth)
+
     # ------------------------------------------------------------------ rank histogram of the evaluation (csrc/eval_metrics.hip)
     def enable_rank_histogram(self, topn, t_cap):
         """From now on every evaluate_step adds its clicks to a device record (cham_eval_rank_hist): hist int64 [t_cap, topn + 1] = valid
@@ -1954,6 +1979,7 @@ class ItemsStateUpdaterHook:
         order per batch - evaluate the baselines on the model's candidate rows (EVAL, :1607-1613), let them learn the batch (both modes,
         :1627-1631), then the state update; their state (``eval_benchmarks_state``, a baselines.DeviceBaselines that outlives the hook) is
         snapshotted and restored with the clicked-items state; end() merges 'hitrate_at_n_<name>' / 'mrr_at_n_<name>' into the results.
+      * in ``ModeKeys.PREDICT`` (Estimator.predict) before_run feeds the state; nothing is fetched, logged, snapshotted or updated.
     Out of scope: the ItemKNN ('item_knn') and undecayed SessionKNN ('sknn') baselines and the reference's dict form of ``eval_benchmark_classifiers``,
     the baselines' beyond-accuracy and cold-start records, the metrics the reference defines but does not instantiate."""
 
@@ -1983,6 +2009,8 @@ class ItemsStateUpdaterHook:
         self.eval_beyond_accuracy_metrics = eval_beyond_accuracy_metrics
 
     def begin(self):
+        if self.mode == ModeKeys.PREDICT:      # feeds the state (before_run) and does nothing else
+            return
         if self.eval_benchmark_classifiers:
             if self._data_parallel():
                 raise ValueError("eval_benchmarks: the baseline recommenders are not available in a data-parallel run")
@@ -2049,9 +2077,13 @@ class ItemsStateUpdaterHook:
         for name in self.articles_metadata:
             if name in m.ph_articles_metadata:
                 feed_dict[m.ph_articles_metadata[name]] = self.articles_metadata[name]
+        if self.mode == ModeKeys.PREDICT:      # the state is fed, nothing is fetched (there are no labels), nothing is updated
+            return SessionRunArgs(fetches={}, feed_dict=feed_dict)
         return SessionRunArgs(fetches=fetches, feed_dict=feed_dict)
 
     def after_run(self, run_context, run_values):
+        if self.mode == ModeKeys.PREDICT:
+            return
         r = run_values.results
         clicked_items = r['clicked_items']
         clicked_timestamps = np.squeeze(r['clicked_timestamps'], axis=-1)
@@ -2192,6 +2224,8 @@ class ItemsStateUpdaterHook:
                                                                         recommender='chameleon'))
 
     def end(self, session=None):
+        if self.mode == ModeKeys.PREDICT:
+            return
         if self.mode == ModeKeys.EVAL and self._data_parallel():
             self._reduce_data_parallel_eval()
         if self.mode == ModeKeys.EVAL:                                         # :1669-1695

@@ -124,6 +124,13 @@ def define_flags():
     a('--eval_benchmarks_max_pairs', type=int, default=1 << 25,
       help="ceiling of the (item, item) entries each learned baseline (coocurrent, sr) may hold in device memory, 32 bytes per entry at "
            "the table's load of 1/2; the run stops with an error beyond it")
+    a('--predict_set_path_regex', default='',
+      help="session files whose sessions get a top-n recommendation after the train / evaluate loop, with the final weights and "
+           "recent-clicks state: for each session the --predict_top_n articles of the recent-clicks buffer most likely to follow its "
+           "last click, the session's own clicks excluded, one JSON line per session in --predict_output_jsonl.  Empty (default): "
+           "nothing is predicted.  Not available under data parallelism")
+    a('--predict_top_n', type=int, default=10, help='length of the recommendation lists of --predict_set_path_regex (1..64)')
+    a('--predict_output_jsonl', default='', help="output file of --predict_set_path_regex (default: <model_dir>/predictions.jsonl)")
     return ap
 
 
@@ -216,8 +223,11 @@ def nar_module_model_fn(features, labels, mode, params):
     elif mode == ModeKeys.EVAL:
         negative_samples = params['eval_total_negative_samples']
         negative_sample_from_buffer = params['eval_negative_samples_from_buffer']
+    elif mode == ModeKeys.PREDICT:      # the input-click stages run on the evaluation's plan shape (Estimator.predict)
+        negative_samples = params['eval_total_negative_samples']
+        negative_sample_from_buffer = params['eval_negative_samples_from_buffer']
     else:
-        raise ValueError("mode %r: the reference defines TRAIN and EVAL only" % (mode,))
+        raise ValueError("mode %r: one of ModeKeys.TRAIN, EVAL, PREDICT" % (mode,))
     dropout_keep_prob = params['dropout_keep_prob'] if mode == ModeKeys.TRAIN else 1.0
     internal_features_config = params.get('internal_features_config') or get_internal_enabled_features_config()
     eval_metrics_top_n = params['eval_metrics_top_n']
@@ -259,6 +269,10 @@ def nar_module_model_fn(features, labels, mode, params):
                                    eval_metrics_by_session_position=params['eval_metrics_by_session_position'],
                                    eval_cold_start=params['eval_cold_start'], eval_metric_ops=eval_metrics,
                                    eval_beyond_accuracy_metrics=params.get('eval_beyond_accuracy_metrics', False))]
+    if mode == ModeKeys.PREDICT:
+        # a chunk of candidates takes no more candidate rows than a training step of this model
+        model.predict_train_negative_samples = params['train_total_negative_samples']
+        return EstimatorSpec(mode, predictions=model, prediction_hooks=hooks)
     if mode == ModeKeys.TRAIN:
         return EstimatorSpec(mode, loss=model.loss_t, train_op=model.train, training_chief_hooks=hooks)
     return EstimatorSpec(mode, loss=model.loss_t, eval_metric_ops=eval_metrics, evaluation_hooks=hooks)
@@ -339,6 +353,12 @@ def _train_and_evaluate_loop(rank, world, ace, articles_metadata, articles_featu
     global clicked_items_state, eval_sessions_metrics_log, sessions_negative_items_log
     global sessions_chameleon_recommendations_log, global_eval_hour_id, eval_benchmarks_state
     benchmarks = eval_benchmarks_from_flags(FLAGS)
+    predict_regex = getattr(FLAGS, 'predict_set_path_regex', '') or ''
+    if predict_regex:
+        from .predict import check_top_n
+        check_top_n(FLAGS.predict_top_n)
+        if world > 1:
+            raise ValueError("--predict_set_path_regex: prediction runs on one process, not under data parallelism (WORLD_SIZE=%d)" % world)
     if world > 1:
         for flag in _DATA_PARALLEL_REFUSED_LISTS:
             if getattr(FLAGS, flag, None):
@@ -403,7 +423,24 @@ def _train_and_evaluate_loop(rank, world, ace, articles_metadata, articles_featu
         _append_json_lines(os.path.join(FLAGS.model_dir, 'eval_chameleon_recommendations_log.json'),
                            [dict(eval_hour_id=global_eval_hour_id, **r) for r in sessions_chameleon_recommendations_log])
     info('INFO:==== Finalized TRAINING Loop elapsed {:.1f} minutes'.format((time() - start_train) / 60.0), flush=True)
+    if predict_regex:
+        out_path = FLAGS.predict_output_jsonl or os.path.join(FLAGS.model_dir, 'predictions.jsonl')
+        n_sessions = write_predictions(model, input_fn(resolve_files(predict_regex)), FLAGS.predict_top_n, out_path)
+        info('INFO:predicted top-{} for {} sessions -> {}'.format(FLAGS.predict_top_n, n_sessions, out_path), flush=True)
     return model
+
+
+def write_predictions(estimator, input_fn, top_n, path):
+    """Estimator.predict over input_fn's sessions, one JSON line per session: session_id, item_ids, scores, probs (the padding of a short
+    list - id 0 - is left out).  Returns the number of sessions written."""
+    count = 0
+    with open(path, 'w') as fh:
+        for r in estimator.predict(input_fn, predict_top_n=top_n):
+            keep = r['item_ids'] != 0
+            fh.write(json.dumps({'session_id': int(r['session_id']), 'item_ids': r['item_ids'][keep].tolist(),
+                                 'scores': [float(x) for x in r['scores'][keep]], 'probs': [float(x) for x in r['probs'][keep]]}) + '\n')
+            count += 1
+    return count
 
 
 def main(argv=None):

@@ -756,6 +756,31 @@ int cham_vsknn_scores(const int64_t* item_clicked, const int64_t* label_next, co
                       const int32_t* items, const int32_t* lens, const int32_t* order, int S, int L, int sample, int knn, double* score,
                       uint8_t* scored, double* sim_out, int32_t* n_out, void* stream);
 
+/* --- Top-n prediction for open sessions (NARModuleModel.predict_step; csrc/predict.hip).  No float atomics: results
+ * depend on the inputs and on the chunk order 0 .. ceil(K / Nc) - 1 alone.
+ *   candidates   the distinct ids in [1, n_items) of buf_ids int64 [n] (zeros, repeats and ids out of range anywhere), ascending, into
+ *                cand int64 [cap] (entries beyond cap are dropped, still counted); K_out int32 [1] (device) = their number.  A presence map
+ *                over n_items and an ordered compaction by prefix scan in ws (candidates_workspace_bytes; n_items < 2^31 - 4096).
+ *   fill_chunk   chunk j of width Nc as the sampler outputs of a plan with P positions and N = Nc negatives: neg_ids int64 [P, Nc] =
+ *                cand[j Nc + i] (the pad item 0 where j Nc + i >= K_dev[0]), neg_slot int32 [P, Nc] = i, pool int64 [pmax] = the same ids
+ *                in slots [0, Nc), 0 beyond (pmax >= Nc).
+ *   topn_merge   merges chunk j's scores logits fp32 [P, 1 + Nc] (column 0, the label column, is ignored) into the running state of each
+ *                row: top_id int64 / top_score fp32 [P, n] in rank order (1 <= n <= 64; start: 0 / -inf) and ms fp32 [P, 2] = {m, s}, the
+ *                running max of score / temperature and the sum of exp(score / temperature - m) (start: -inf, 0), over the candidates that
+ *                are not masked.  Masked: the columns with j Nc + i >= K_dev[0], an id that occurs in the row's excl int64 [P, T]
+ *                (T <= 128; its zeros never match), a score that is not finite.  Order: score descending, then id ascending.  One wave per
+ *                row, ranking by counting, every loop bounded by Nc, T or a constant.  The chunks of one prediction are merged in the
+ *                order j = 0, 1, ...: (m, s) accumulate in that order.
+ *   topn_finish  probs fp32 [P, n] = exp(top_score / temperature - m) / s, 0 at the padding entries (score -inf). */
+size_t cham_predict_candidates_workspace_bytes(int64_t n_items);
+int cham_predict_candidates(const int64_t* buf_ids, int n, int64_t n_items, int64_t* cand, int64_t cap, int32_t* K_out, void* ws,
+                            size_t ws_bytes, void* stream);
+int cham_predict_fill_chunk(const int64_t* cand, const int32_t* K_dev, int j, int Nc, int P, int pmax, int64_t* neg_ids, int32_t* neg_slot,
+                            int64_t* pool, void* stream);
+int cham_predict_topn_merge(const float* logits, const int64_t* cand, const int32_t* K_dev, int j, int Nc, const int64_t* excl, int T, int P,
+                            int n, float softmax_temperature, int64_t* top_id, float* top_score, float* ms, void* stream);
+int cham_predict_topn_finish(const float* top_score, const float* ms, int P, int n, float softmax_temperature, float* probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
