@@ -172,6 +172,8 @@ _SIGNATURES = {
     "cham_predict_fill_chunk": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P]),
     "cham_predict_topn_merge": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, c_int, c_float, P, P, P, P]),
     "cham_predict_topn_finish": (c_int, [P, P, c_int, c_int, c_float, P, P]),
+    "cham_eval_full_rank_merge": (c_int, [P, P, P, c_int, c_int, P, P, P, c_int, c_int, P, P, P]),
+    "cham_eval_full_rank_scatter": (c_int, [P, P, P, c_int, P, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

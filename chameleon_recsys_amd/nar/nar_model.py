@@ -849,7 +849,8 @@ class NARModuleModel:
         self._ba = None                        # enable_beyond_accuracy_metrics: launch scalars; _ba_buffers: maps, counts, per-click values
         self._ba_buffers = None
         self._rh = None                        # enable_rank_histogram: the device record of cham_eval_rank_hist
-        self.dp = None                         # parallel.DataParallelNAR.attach: the data-parallel wrapper this model's batches go through
+        self._fr = None                        # enable_full_candidate_ranking: the record and the last batch's ranks (nar/full_eval.py)
+        self.dp = None                        # parallel.DataParallelNAR.attach: the data-parallel wrapper this model's batches go through
         # attributes ItemsStateUpdaterHook fetches / feeds (nar_model.py:1435-1467)
         inp = lambda k: Tensor(k, lambda: np.asarray(self.inputs[k]))
         self.item_clicked = inp('item_clicked')
@@ -1658,6 +1659,13 @@ class NARModuleModel:
             self._rank_histogram(d)
         if self._ba is not None:
             self._beyond_accuracy(d)
+        if self._fr is not None:      # after the step's own records: nothing above reads what this leaves
+            from . import full_eval
+            depth = _roctx.depth()
+            try:
+                full_eval.rank_step(self, pl, d)
+            finally:
+                _roctx.unwind(depth)
         self._eval_iter += 1
         return self.total_loss
 
@@ -1728,6 +1736,37 @@ class NARModuleModel:
     def rank_histogram(self):
         """(hist [t_cap, topn + 1] int64, pop_sum [t_cap] float64) as numpy: what the evaluate_steps since enable_rank_histogram added."""
         return self._rh['hist'].cpu().numpy(), self._rh['pop_sum'].cpu().numpy()
+
+    # ------------------------------------------------------------------ full-candidate evaluation (nar/full_eval.py, csrc/eval_full.hip)
+    def enable_full_candidate_ranking(self, topn, t_cap, chunk_candidates=None, block_rows=None, return_scores=False):
+        """From now on every evaluate_step also ranks each valid click's label against EVERY distinct id of the fed recent-clicks buffer
+        (the session's own ids excluded) and adds the ranks to a second cham_eval_rank_hist record (bounds and
+        shapes: enable_rank_histogram).  Allocates and zeroes the record.  Tests only: chunk_candidates / block_rows override the chunk
+        width and the row-block size, return_scores keeps per click the [K] scores and the label's logit of every chunk."""
+        from . import full_eval
+        self._fr = full_eval.new_record(self, topn, t_cap, chunk_candidates, block_rows, return_scores)
+
+    def reserve_full_candidate_ranking(self, T):
+        """Make room for batches of T click positions (reserve_rank_histogram's rule: a longer record, the counts so far kept)."""
+        from . import full_eval
+        full_eval.check_session_length(T)
+        fr = self._fr
+        if T > fr['t_cap']:
+            t_cap = max(int(T), 2 * fr['t_cap'])
+            hist = torch.zeros(t_cap, fr['topn'] + 1, dtype=torch.int64, device=self.rt.device)
+            pop_sum = torch.zeros(t_cap, dtype=torch.float64, device=self.rt.device)
+            hist[:fr['t_cap']].copy_(fr['hist'])
+            pop_sum[:fr['t_cap']].copy_(fr['pop_sum'])
+            fr.update(t_cap=t_cap, hist=hist, pop_sum=pop_sum)
+
+    def full_rank_histogram(self):
+        """(hist [t_cap, topn + 1] int64, pop_sum [t_cap] float64) as numpy: the full-candidate ranks since enable_full_candidate_ranking."""
+        return self._fr['hist'].cpu().numpy(), self._fr['pop_sum'].cpu().numpy()
+
+    def full_rank_outputs(self):
+        """The last evaluate_step's label_rank and competitors (int32 [B, T] numpy; rank -1 at padded positions) + K, Nc, blocks, chunks."""
+        from . import full_eval
+        return full_eval.outputs(self)
 
     # ------------------------------------------------------------------ beyond-accuracy evaluation metrics (csrc/eval_metrics.hip)
     def enable_beyond_accuracy_metrics(self, topn, relevance_positive_sample, relevance_negative_samples, recent_clicks_buffer):
@@ -1979,6 +2018,10 @@ class ItemsStateUpdaterHook:
         order per batch - evaluate the baselines on the model's candidate rows (EVAL, :1607-1613), let them learn the batch (both modes,
         :1627-1631), then the state update; their state (``eval_benchmarks_state``, a baselines.DeviceBaselines that outlives the hook) is
         snapshotted and restored with the clicked-items state; end() merges 'hitrate_at_n_<name>' / 'mrr_at_n_<name>' into the results.
+      * ``eval_full_candidates`` (off by default): begin() enables the model's full-candidate ranking in EVAL, before_run
+        reserves its record for the batch's T, evaluate_step ranks every valid click against every distinct id of the fed recent-clicks
+        buffer, end() merges 'hitrate_at_n_chameleon_full', 'mrr_at_n_chameleon_full', 'ndcg_at_n_chameleon_full' (+ the per-position hit
+        rates) and 'full_candidates_mean' into the results; refused by begin() under an active data-parallel wrapper.
       * in ``ModeKeys.PREDICT`` (Estimator.predict) before_run feeds the state; nothing is fetched, logged, snapshotted or updated.
     Out of scope: the ItemKNN ('item_knn') and undecayed SessionKNN ('sknn') baselines and the reference's dict form of ``eval_benchmark_classifiers``,
     the baselines' beyond-accuracy and cold-start records, the metrics the reference defines but does not instantiate."""
@@ -1987,8 +2030,9 @@ class ItemsStateUpdaterHook:
                  sessions_negative_items_log=None, sessions_chameleon_recommendations_log=None,
                  content_article_embeddings_matrix=None, articles_metadata=None, eval_negative_sample_relevance=None,
                  eval_benchmark_classifiers=[], eval_metrics_by_session_position=False, eval_cold_start=False,
-                 eval_metric_ops=None, eval_beyond_accuracy_metrics=False, eval_benchmarks_state=None):
+                 eval_metric_ops=None, eval_beyond_accuracy_metrics=False, eval_benchmarks_state=None, eval_full_candidates=False):
         from .baselines import BASELINE_NAMES
+        self.eval_full_candidates = bool(eval_full_candidates)
         if eval_benchmark_classifiers and not (isinstance(eval_benchmark_classifiers, (list, tuple)) and
                                                all(isinstance(x, str) and x in BASELINE_NAMES for x in eval_benchmark_classifiers)):
             raise NotImplementedError("baseline recommenders (nar/benchmarks) are out of scope: pass --disable_eval_benchmarks")
@@ -2011,6 +2055,8 @@ class ItemsStateUpdaterHook:
     def begin(self):
         if self.mode == ModeKeys.PREDICT:      # feeds the state (before_run) and does nothing else
             return
+        if self.eval_full_candidates and self._data_parallel():
+            raise ValueError("--eval_full_candidates: the full-candidate evaluation runs on one process, not under data parallelism")
         if self.eval_benchmark_classifiers:
             if self._data_parallel():
                 raise ValueError("eval_benchmarks: the baseline recommenders are not available in a data-parallel run")
@@ -2038,6 +2084,8 @@ class ItemsStateUpdaterHook:
                                                           st.buf_ids if getattr(st, 'is_device', False) else host_buffer)
             if self.eval_metrics_by_session_position:
                 self.streaming_metrics.append(HitRateBySessionPosition(self.eval_metrics_top_n))
+            if self.eval_full_candidates:
+                self.model.enable_full_candidate_ranking(self.eval_metrics_top_n, 32)
             self.stats_logs = []
             if self._data_parallel():
                 # every rank evaluates its own rows of every batch: the accuracy metrics come from the device-side rank histogram, summed
@@ -2063,6 +2111,8 @@ class ItemsStateUpdaterHook:
                    'next_item_labels': m.next_item_label, 'last_item_label': m.label_last_item,
                    'session_id': m.session_id, 'user_id': m.user_id}
         dp_eval = self.mode == ModeKeys.EVAL and self._data_parallel()
+        if self.eval_full_candidates and self.mode == ModeKeys.EVAL:
+            m.reserve_full_candidate_ranking(np.asarray(m.inputs['item_clicked']).shape[1])
         if dp_eval:      # the ranked lists stay on the device (a rank without rows of this batch has none)
             fetches.update(batch_items_count=m.batch_items_count, batch_unique_items_count=m.batch_unique_items_count)
             m.reserve_rank_histogram(np.asarray(m.inputs['item_clicked']).shape[1])
@@ -2235,6 +2285,9 @@ class ItemsStateUpdaterHook:
                 self.eval_streaming_metrics_last['coldstart_chameleon'] = self.clicked_items_state.get_cold_start_state().get_statistics()
             if self.baselines is not None:
                 self.eval_streaming_metrics_last.update(self.baselines.results(self.eval_metrics_top_n, self.eval_metrics_by_session_position))
+            if self.eval_full_candidates:
+                from . import full_eval
+                self.eval_streaming_metrics_last.update(full_eval.results(self.model, self.eval_metrics_by_session_position))
             self.eval_sessions_metrics_log.append(self.eval_streaming_metrics_last)
             self.clicked_items_state.restore_state_checkpoint()
         if self.baselines is not None:

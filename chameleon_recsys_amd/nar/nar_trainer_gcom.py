@@ -113,6 +113,11 @@ def define_flags():
     a('--eval_beyond_accuracy_metrics', type=_bool, default=False, nargs='?', const=True,
       help="also report NDCG@n, item coverage, ESI-R / ESI-RR novelty and content EILD-R / EILD-RR diversity (the reference's "
            "create_eval_metrics list, nar_model.py:1709-1719; computed on the GPU); --eval_negative_sample_relevance weights the -RR pair")
+    a('--eval_full_candidates', type=_bool, default=False, nargs='?', const=True,
+      help="also rank every evaluated click against EVERY distinct article of the recent-clicks buffer (the session's own articles "
+           "excluded) instead of --eval_total_negative_samples sampled ones: hitrate_at_n_chameleon_full, mrr_at_n_chameleon_full, "
+           "ndcg_at_n_chameleon_full and full_candidates_mean (the mean size of that set) beside the sampled metrics.  Costs about "
+           "(candidates / (1 + eval negatives)) evaluation forwards of the candidate rows per batch.  Not available under data parallelism")
     a('--clicked_items_state', default='host', choices=['host', 'device'], help="keep the recent-clicks state in host numpy (reference "
       "class) or in HBM (bit-identical, no host round trip per step)")
     a('--eval_benchmarks', type=_list, default=[],
@@ -268,7 +273,8 @@ def nar_module_model_fn(features, labels, mode, params):
                                    eval_benchmarks_state=params.get('eval_benchmarks_state') or eval_benchmarks_state,
                                    eval_metrics_by_session_position=params['eval_metrics_by_session_position'],
                                    eval_cold_start=params['eval_cold_start'], eval_metric_ops=eval_metrics,
-                                   eval_beyond_accuracy_metrics=params.get('eval_beyond_accuracy_metrics', False))]
+                                   eval_beyond_accuracy_metrics=params.get('eval_beyond_accuracy_metrics', False),
+                                   eval_full_candidates=params.get('eval_full_candidates', False))]
     if mode == ModeKeys.PREDICT:
         # a chunk of candidates takes no more candidate rows than a training step of this model
         model.predict_train_negative_samples = params['train_total_negative_samples']
@@ -300,6 +306,7 @@ def build_estimator(model_dir, content_article_embeddings_matrix, articles_metad
         'novelty_reg_factor': FLAGS.novelty_reg_factor, 'diversity_reg_factor': FLAGS.diversity_reg_factor,
         'eval_negative_sample_relevance': FLAGS.eval_negative_sample_relevance, 'eval_cold_start': FLAGS.eval_cold_start,
         'eval_beyond_accuracy_metrics': FLAGS.eval_beyond_accuracy_metrics,
+        'eval_full_candidates': getattr(FLAGS, 'eval_full_candidates', False),
         'loss_function': FLAGS.loss_function, 'bpr_max_reg': FLAGS.bpr_max_reg,
         'eval_benchmarks': eval_benchmarks_from_flags(FLAGS),
         'session_features_config': session_features_config, 'articles_features_config': articles_features_config,
@@ -359,6 +366,9 @@ def _train_and_evaluate_loop(rank, world, ace, articles_metadata, articles_featu
         check_top_n(FLAGS.predict_top_n)
         if world > 1:
             raise ValueError("--predict_set_path_regex: prediction runs on one process, not under data parallelism (WORLD_SIZE=%d)" % world)
+    if world > 1 and getattr(FLAGS, 'eval_full_candidates', False):
+        raise ValueError("--eval_full_candidates: the full-candidate evaluation runs on one process, not under data parallelism "
+                         "(WORLD_SIZE=%d)" % world)
     if world > 1:
         for flag in _DATA_PARALLEL_REFUSED_LISTS:
             if getattr(FLAGS, flag, None):

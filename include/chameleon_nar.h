@@ -781,6 +781,19 @@ int cham_predict_topn_merge(const float* logits, const int64_t* cand, const int3
                             int n, float softmax_temperature, int64_t* top_id, float* top_score, float* ms, void* stream);
 int cham_predict_topn_finish(const float* top_score, const float* ms, int P, int n, float softmax_temperature, float* probs, void* stream);
 
+/* --- Full-candidate evaluation (--eval_full_candidates; csrc/eval_full.hip).  Integer counts only: no float
+ * arithmetic, no atomics, independent of any order.
+ *   rank_merge    adds chunk j's share to the two counters of each of R rows (one row = one valid click; T1 <= 128): logits fp32
+ *                 [R, 1 + Nc] (column 0 = the label's logit z_l, column 1 + i = candidate cand[j Nc + i]; columns with j Nc + i >=
+ *                 K_dev[0] are skipped).  A candidate competes unless it is labels[r] or occurs in aci int64 [B, T1] row row_session[r];
+ *                 competitors[r] += their number, beat[r] += those with not (z_c < z_l or (z_c == z_l and id_c > label)) - a NaN on
+ *                 either side counts against the label.  The caller zeroes beat / competitors before a row block's first chunk.
+ *   rank_scatter  label_rank[rows[i]] = beat[i], n_comp[rows[i]] = competitors[i] for i < R_valid (rows[i] = b T + t). */
+int cham_eval_full_rank_merge(const float* logits, const int64_t* cand, const int32_t* K_dev, int j, int Nc, const int64_t* labels,
+                              const int32_t* row_session, const int64_t* aci, int T1, int R, int32_t* beat, int32_t* competitors, void* stream);
+int cham_eval_full_rank_scatter(const int32_t* beat, const int32_t* competitors, const int32_t* rows, int R_valid, int32_t* label_rank,
+                                int32_t* n_comp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
